@@ -17,6 +17,17 @@ renders all 256 frames of its 1/N of the tiles), with the reduce timed on
 its own.  ``--config c4`` makes that the headline (``scaling: strong``);
 ``--config c2|c5|c1`` bench the other single-GPU configs.
 
+A plain run does what the headline needs and no more: set up, warm up, time
+``--steps`` steps, print the line (metric, value, unit, ms_per_step, config).
+``--full`` adds every other leg and check, each outside the timed region: the
+instrumented run's counters and the roofline / HBM accounting from them, the
+solo-pipeline kernel times, the table scene kernel and value edit legs, the
+display pass, the image readback, rank 0's tile check (and ``--validate``),
+the per-rank render and reduce times, the ``c4_strong`` leg and the CPU
+baseline.  ``--dump-outputs DIR`` (either kind of run) writes the image a
+caller holds after the last timed step to ``DIR/image.npy``, and the few
+non-finite channels it holds by the contract (0 there) to ``DIR/nonfinite.npy``.
+
 Prints ONE JSON line (rank 0).  See DESIGN.md 5 for the roofline accounting.
 """
 from __future__ import annotations
@@ -811,7 +822,19 @@ def main() -> None:
     ap.add_argument("--no-table-kernel", action="store_true",
                     help="skip the one-GPU timing of the table scene kernel (jit_bake 0: what a value-editing "
                          "session runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg and check beside the headline (counters and roofline, solo pipeline, "
+                         "table kernel, value edit, display, readback, tile check, per-rank and reduce times, "
+                         "c4_strong, CPU baseline); without it the other options of those legs have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image as it stands after the last timed step to DIR/image.npy (float32 "
+                         "[height][width][4]; a fixed seeded sample of texels, [n][4], above DUMP_LIMIT bytes), "
+                         "non-finite channels as 0 there and listed in DIR/nonfinite.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.validate and not args.full:
+        ap.error("--validate is one of the --full checks: pass --full with it")
     world, launch = resolve_world(args.gpus)
     if launch:
         # N ranks from one command line: torch.distributed.run as a child
@@ -883,9 +906,11 @@ def main() -> None:
         tr.step(spp)
         tr.reduce(0)  # RCCL sum of the tile images onto rank 0 (no-op at world 1)
 
-    # algorithmic work per step from the instrumented kernel (outside timing)
-    st = pt.stats(N.Constants(time=0.0, frame=1, aspect=aspect, last_clear=1), spp_step)
-    taps = pt.tap_stats()  # the shade pass's normal-tap share of st
+    st = taps = None
+    if args.full:
+        # algorithmic work per step from the instrumented kernel (outside timing)
+        st = pt.stats(N.Constants(time=0.0, frame=1, aspect=aspect, last_clear=1), spp_step)
+        taps = pt.tap_stats()  # the shade pass's normal-tap share of st
 
     for _ in range(args.warmup):
         step()
@@ -920,6 +945,47 @@ def main() -> None:
     pt.sync()
     barrier()
     dt = max_over_ranks(dist, time.perf_counter() - t0, dev)
+    pixels = width * height
+    samples_step = pixels * spp * (world if scaling == "weak" else 1)  # all ranks
+    value = samples_step * args.steps / dt / 1e6
+    ms_step = dt * 1e3 / args.steps
+
+    def finish(out):
+        if out is not None:
+            out["full"] = bool(args.full)
+            # the line says itself whether it may be trusted (a consumer reading
+            # only the JSON sees it, not just the exit status)
+            fails = validation_failures(out)
+            out["valid"] = not fails
+            out["invalid_reasons"] = fails
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            barrier()
+            dist.destroy_process_group()
+        rc = exit_status(out)
+        if rc:
+            sys.exit(rc)
+
+    dumped = None
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step: the
+        # accumulation image (every rank takes part in the reduce at N > 1)
+        last = tr.image(0)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, last)
+    if not args.full:
+        out = None
+        if rank == 0:
+            n_chunks = float(np.mean(chunks)) if chunks else float(pt.get_option("bin_chunks"))
+            out = headline(args, pt, scene_name, width, height, bounces, spp, world, scaling, value, ms_step,
+                           n_chunks)
+            out["rccl_ranks"] = rccl_ranks
+            out["reduce_backend"] = mode if world > 1 else None
+            if dumped is not None:
+                out["outputs"] = dumped
+        pt.close()
+        finish(out)
+        return
     # the table of check[] sets after the last timed dispatch:
     # the distinct sets its last chunk saw (of PT_BINS slots) and the sets
     # that found no slot and shared a hash bin (-1: no table in use)
@@ -965,11 +1031,6 @@ def main() -> None:
     if table is not None:
         table.update(value_edit_leg(pt, prog))
 
-    pixels = width * height
-    samples_step = pixels * spp * (world if scaling == "weak" else 1)  # all ranks
-    value = samples_step * args.steps / dt / 1e6
-    ms_step = dt * 1e3 / args.steps
-
     out = None
     if rank == 0:
         out = report(args, pt, st, taps, prog, scene_name, width, height, bounces, spp, spp_step, world, scaling,
@@ -990,24 +1051,96 @@ def main() -> None:
                          "reads it)"}
         if table is not None:
             out["table_kernel"] = table
+        if dumped is not None:
+            out["outputs"] = dumped
     pt.close()
     if world > 1 and scaling == "weak" and args.c4_steps > 0 and not args.validate:
         leg = strong_leg(local_rank, rank, world, mode, barrier, dist, dev, args.c4_steps, 1)
         if out is not None:
             out["c4_strong"] = leg
-    if out is not None:
-        # the line says itself whether it may be trusted (a consumer reading
-        # only the JSON sees it, not just the exit status)
-        fails = validation_failures(out)
-        out["valid"] = not fails
-        out["invalid_reasons"] = fails
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        barrier()
-        dist.destroy_process_group()
-    rc = exit_status(out)
-    if rc:
-        sys.exit(rc)
+    finish(out)
+
+
+DUMP_LIMIT = 64 * 10 ** 6  # bytes of --dump-outputs' files in all (a 1080p RGBA32F image, 33.2 MB, is written whole)
+DUMP_NONFINITE = 1 << 20  # of them, nonfinite.npy's share: at most DUMP_NONFINITE // 16 - 8 rows
+NONFINITE_CODES = {"nan": 1.0, "+inf": 2.0, "-inf": 3.0}
+
+
+def dump_outputs(path: str, img: np.ndarray) -> dict:
+    """--dump-outputs: the accumulation image after the last timed step, as
+    two files of finite numbers.
+    - DIR/image.npy: float32 [height][width][4].  An image above DUMP_LIMIT -
+      DUMP_NONFINITE bytes is written as a sample instead: the texels (rows
+      of the image flattened to [height * width][4]) at (DUMP_LIMIT -
+      DUMP_NONFINITE) // 16 - 8 indices drawn without replacement by
+      default_rng(0), in ascending order -- the same texels for the same
+      image size, so two builds' files compare element for element.
+    - DIR/nonfinite.npy: float64 [n][2].  The image holds a few non-finite
+      channels by the contract (C3 and C5: NaN from the reference's normalize
+      of a zero vector); image.npy has 0 in their place, and each
+      is a row here: (index of the element in image.npy flattened, code), code
+      1 NaN, 2 +inf, 3 -inf (NONFINITE_CODES), in ascending index order; the
+      first DUMP_NONFINITE // 16 - 8 of them (the line has the whole count).
+    Both files together stay within DUMP_LIMIT.  Returns what was written,
+    for the line."""
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(img, dtype=np.float32)
+    h, w = a.shape[:2]
+    room = DUMP_LIMIT - DUMP_NONFINITE
+    sampled = a.nbytes > room - 128
+    if sampled:
+        n = room // 16 - 8  # (- 8 rows: room for the file's header)
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+        a = a.reshape(h * w, 4)[idx]
+    flat = a.reshape(-1)
+    bad = np.flatnonzero(~np.isfinite(flat))
+    v = flat[bad]
+    code = np.where(np.isnan(v), NONFINITE_CODES["nan"],
+                    np.where(v > 0, NONFINITE_CODES["+inf"], NONFINITE_CODES["-inf"]))
+    rows = np.stack([bad.astype(np.float64), code.astype(np.float64)], axis=1)[:DUMP_NONFINITE // 16 - 8]
+    if bad.size:
+        a = a.copy()
+        a.reshape(-1)[bad] = 0.0
+    np.save(os.path.join(path, "image.npy"), a)
+    np.save(os.path.join(path, "nonfinite.npy"), rows)
+    return {"image": {"file": "image.npy", "shape": list(a.shape), "dtype": "float32", "sampled": sampled,
+                      "of": [h, w, 4]},
+            "nonfinite": {"file": "nonfinite.npy", "shape": list(rows.shape), "dtype": "float64",
+                          "count": int(bad.size), "codes": NONFINITE_CODES}}
+
+
+def headline(args, pt, scene_name, width, height, bounces, spp, world, scaling, value, ms_step, n_chunks) -> dict:
+    """The part of rank 0's line a plain run prints: the metric, its value
+    and ms_per_step over the timed steps, and the configuration they ran."""
+    jit = bool(pt.get_option("jit_active"))
+    data = f"synthetic (scenes.{scenes_fn(scene_name)}"
+    return {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "Msamples/sec",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 3),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": data + ("" if scene_name != "c3" else ": 32-node sdf_editor graph, seed 42") + ")",
+        "config": {"workload": f"{scene_name} {width}x{height}, {bounces} bounces, "
+                               + (f"{spp * world} spp per step ({spp} per GPU-share)" if scaling == "weak"
+                                  else f"{spp} spp per step over all GPUs") + ", progressive accumulate",
+                   "width": width, "height": height, "bounces": bounces,
+                   "spp_per_step": spp * world if scaling == "weak" else spp, "parallelism": f"tiles{world}",
+                   "pipelines": int(pt.get_option("bin_lanes")), "baseline_config": args.config,
+                   "scene_kernel": "values-baked tier (jit_bake 2 tier-up, installed before timing; the table "
+                                   "kernel an editing session runs between value edits: table_kernel)"
+                                   if jit and pt.get_option("jit_tier_active") else
+                                   ("table scene kernel" if jit else "op-list interpreter"),
+                   # chunking (pt_runtime.hip bin_samples: fixed per context from the device's total memory)
+                   "bin_samples": int(pt.get_option("bin_samples")), "chunks_per_dispatch": n_chunks,
+                   "bin_fallback": bool(pt.get_option("bin_fallback"))},
+    }
 
 
 def exit_status(out) -> int:
@@ -1094,33 +1227,8 @@ def report(args, pt, st, taps, prog, scene_name, width, height, bounces, spp, sp
         timing = "the timed dispatches (one kernel)"
     path_tf = flops_step / (d_ms * 1e-3) / 1e12
     achieved_gbs = pipe["total"] / (d_ms * 1e-3) / 1e9  # whole dispatch: every pass's algorithmic bytes
-    data = f"synthetic (scenes.{scenes_fn(scene_name)}"
-    out = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "Msamples/sec",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 3),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": data + ("" if scene_name != "c3" else ": 32-node sdf_editor graph, seed 42") + ")",
-        "config": {"workload": f"{scene_name} {width}x{height}, {bounces} bounces, "
-                               + (f"{spp * world} spp per step ({spp} per GPU-share)" if scaling == "weak"
-                                  else f"{spp} spp per step over all GPUs") + ", progressive accumulate",
-                   "width": width, "height": height, "bounces": bounces,
-                   "spp_per_step": spp * world if scaling == "weak" else spp, "parallelism": f"tiles{world}",
-                   "pipelines": int(pt.get_option("bin_lanes")), "baseline_config": args.config,
-                   "scene_kernel": "values-baked tier (jit_bake 2 tier-up, installed before timing; the table "
-                                   "kernel an editing session runs between value edits: table_kernel)"
-                                   if jit and pt.get_option("jit_tier_active") else
-                                   ("table scene kernel" if jit else "op-list interpreter"),
-                   # chunking (pt_runtime.hip bin_samples: fixed per context from the device's total memory)
-                   "bin_samples": int(pt.get_option("bin_samples")), "chunks_per_dispatch": n_chunks,
-                   "bin_fallback": bool(pt.get_option("bin_fallback"))},
+    out = headline(args, pt, scene_name, width, height, bounces, spp, world, scaling, value, ms_step, n_chunks)
+    out.update({
         "roofline": {"bound": "valu",
                      "bound_note": "FP32 vector ALU: no dense contraction on this path, so no MFMA, and arithmetic "
                                    "intensity ~65 flop/B of measured traffic is above the HBM ridge; the metric's "
@@ -1158,7 +1266,7 @@ def report(args, pt, st, taps, prog, scene_name, width, height, bounces, spp, sp
                 # 1: the scene kernels came from the shipped cache (lib/jitcache), 0: this process compiled them
                 "from_shipped_cache": int(pt.get_option("jit_cache")),
                 "shade_waves_per_simd": pt.get_option("jit_shade_waves")},
-    }
+    })
     if shade is not None:
         out["roofline"]["shade"] = shade
         # the two kernels' executed fractions while they share the GPU (the

@@ -5,6 +5,8 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+# (--full: parse_bench.py prints the roofline and schedule fields of the full line)
+AB_ARGS="--full ${AB_ARGS:-}"
 IFS=";" read -ra VARS <<< "${AB_VARIANTS:-PT_JIT_DEFS=;PT_JIT_DEFS=}"
 for v in "${VARS[@]}"; do
   env $v timeout -k 10 300 python bench.py --steps ${AB_STEPS:-3} --warmup 1 --no-cpu-baseline ${AB_ARGS:-} > gpurun_out/ab.tmp 2>&1

@@ -25,6 +25,6 @@ if [ "${CONFIGS:-0}" = 1 ]; then
   rc=$?; echo "configs rc=$rc"; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  (cd "$D" && timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "$GPU_OUT/${T}_bench.log" 2>&1)
+  (cd "$D" && timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "$GPU_OUT/${T}_bench.log" 2>&1)
   rc=$?; echo "bench rc=$rc"; python "$R/scripts/parse_bench.py" "$GPU_OUT/${T}_bench.log" | cut -c1-200; exit $rc
 fi

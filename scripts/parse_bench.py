@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
-"""Print the key fields of the last JSON line of a bench.py log."""
+"""Print the key fields of the last JSON line of a bench.py log: the value
+and ms_per_step of any line, and of a --full line the per-launch kernel
+times, roofline fractions, schedule and cull figures."""
 import json
 import sys
 
 line = [l for l in open(sys.argv[1]).read().splitlines() if l.startswith("{")][-1]
 d = json.loads(line)
+if "roofline" not in d:  # a plain run's line
+    print(d["value"], "ms_per_step", d.get("ms_per_step"))
+    sys.exit(0)
 w = d.get("work", {})
 cull = {}
 if w.get("xform_shape"):

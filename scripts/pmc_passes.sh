@@ -12,7 +12,7 @@ i=0
 for p in "${PASSES[@]}"; do
   i=$((i+1))
   timeout -s KILL 150 rocprofv3 --pmc $p --kernel-trace -d "$OUT/p$i" -o pmc --output-format csv -- \
-      python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu-baseline ${PMC_ARGS:-} > "$OUT/p${i}.log" 2>&1
+      python3 "$R/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline ${PMC_ARGS:-} > "$OUT/p${i}.log" 2>&1
   rc=$?; echo "pass $i rc=$rc ($p)"
   [ $rc -eq 0 ] || exit $rc
 done

@@ -12,10 +12,10 @@ D="$R"; [ -n "${TREE:-}" ] && D="$R/ab/$TREE"
 T=${TAG:?TAG}
 O="$R/gpurun_out"; mkdir -p "$O"
 for n in 2 4; do
-  (cd "$D" && PT_BENCH_SHARE_GPU=1 OMP_NUM_THREADS=4 timeout -k 10 600 python bench.py --gpus $n --dist-backend gloo \
+  (cd "$D" && PT_BENCH_SHARE_GPU=1 OMP_NUM_THREADS=4 timeout -k 10 600 python bench.py --full --gpus $n --dist-backend gloo \
      ${RANK_ARGS:---steps 2 --warmup 1 --no-cpu-baseline --c4-steps 1} \
      > "$O/${T}_mgpu_rehearsal_${n}rank.log" 2>&1)
   rc=$?; echo "ranks $n rc=$rc"; tail -c 300 "$O/${T}_mgpu_rehearsal_${n}rank.log"; [ $rc -eq 0 ] || exit $rc
 done
-(cd "$D" && timeout -k 10 400 python bench.py --config c4 --steps 2 --warmup 1 --no-cpu-baseline > "$O/${T}_bench_c4.log" 2>&1)
+(cd "$D" && timeout -k 10 400 python bench.py --full --config c4 --steps 2 --warmup 1 --no-cpu-baseline > "$O/${T}_bench_c4.log" 2>&1)
 rc=$?; echo "c4 rc=$rc"; tail -c 300 "$O/${T}_bench_c4.log"; exit $rc

@@ -183,7 +183,7 @@ def main(tag: str, src: str = None) -> None:
     with open(os.path.join(dst, f"{tag}_pmc.json"), "w") as f:
         json.dump(out, f, indent=1)
     lines = [f"# rocprofv3 summary `{tag}`", "",
-             f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py {bench_line['steps'] if bench_line else ''}`"
+             f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps {bench_line['steps'] if bench_line else ''}`"
              " (see scripts/profile.sh); PMC passes one counter group each.", "",
              "## Kernel stats", "", "| kernel | calls | avg ms | % |", "|---|---|---|---|"]
     for r in stats:

@@ -107,6 +107,60 @@ def test_gpus_mismatch_exits_before_the_gpu():
     assert "WORLD_SIZE=2" in r.stderr and not any(l.startswith("{") for l in r.stdout.splitlines())
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: image.npy is the float32 image bit for bit but for its
+    non-finite channels, which are 0 there and rows of nonfinite.npy (so both
+    files are finite and the image can be put together again); above the
+    limit a fixed sample of its texels, the same on every call, both files
+    within DUMP_LIMIT."""
+    import os
+
+    img = np.random.default_rng(7).random((40, 40, 4)).astype(np.float32)
+    img[3, 5] = np.nan
+    img[7, 1, 2], img[7, 1, 3] = np.inf, -np.inf
+    keep = img.copy()
+    info = bench.dump_outputs(str(tmp_path / "a"), img)
+    assert np.array_equal(img.view(np.uint32), keep.view(np.uint32))  # (the caller's image is left alone)
+    got, nf = np.load(tmp_path / "a" / "image.npy"), np.load(tmp_path / "a" / "nonfinite.npy")
+    assert got.dtype == np.float32 and nf.dtype == np.float64 and np.isfinite(got).all() and np.isfinite(nf).all()
+    at = [(3 * 40 + 5) * 4 + k for k in range(4)] + [(7 * 40 + 1) * 4 + 2, (7 * 40 + 1) * 4 + 3]
+    assert nf.tolist() == [[float(i), c] for i, c in zip(at, [1.0] * 4 + [2.0, 3.0])]
+    assert info["nonfinite"]["count"] == 6 and info["nonfinite"]["shape"] == [6, 2]
+    back = got.copy().reshape(-1)
+    assert not back[nf[:, 0].astype(int)].any()
+    back[nf[:, 0].astype(int)] = np.array([0, np.nan, np.inf, -np.inf], np.float32)[nf[:, 1].astype(int)]
+    fin = np.isfinite(img)
+    assert np.array_equal(back.reshape(img.shape)[fin].view(np.uint32), img[fin].view(np.uint32))
+    assert np.array_equal(np.isnan(back.reshape(img.shape)), np.isnan(img))
+    assert np.array_equal(back.reshape(img.shape)[~fin & ~np.isnan(img)], img[~fin & ~np.isnan(img)])
+    assert info["image"]["sampled"] is False and info["image"]["shape"] == [40, 40, 4]
+    monkeypatch.setattr(bench, "DUMP_NONFINITE", 16 * 12)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 16 * 12 + 16 * 58)
+    img[:] = np.where(np.arange(40 * 40 * 4).reshape(img.shape) % 7 == 0, np.nan, img)
+    info = bench.dump_outputs(str(tmp_path / "b"), img)
+    bench.dump_outputs(str(tmp_path / "c"), img)
+    b, c = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "c" / "image.npy")
+    nb = np.load(tmp_path / "b" / "nonfinite.npy")
+    assert b.dtype == np.float32 and b.shape == (50, 4) and np.isfinite(b).all()
+    assert nb.shape == (4, 2) and info["nonfinite"]["count"] > 4 and np.array_equal(
+        nb, np.load(tmp_path / "c" / "nonfinite.npy"))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= bench.DUMP_LIMIT
+    assert np.array_equal(b.view(np.uint32), c.view(np.uint32))
+    assert info["image"]["sampled"] is True and info["image"]["of"] == [40, 40, 4]
+    flat = {np.nan_to_num(r, nan=0.0).tobytes() for r in img.reshape(-1, 4)}
+    assert all(r.tobytes() in flat for r in b)
+
+
+def test_validate_needs_full():
+    """--validate is one of the --full checks: a plain run refuses it before
+    it imports the library or touches a GPU."""
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, bench.__file__, "--validate"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
 def test_executed_flops_drop_only_culled_work(counters):
     """roofline.frac's executed flops: each pass's algorithmic flops less its
     culled evaluations, each culled one still paying its test; without culls

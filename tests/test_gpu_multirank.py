@@ -30,7 +30,7 @@ def _free_port() -> int:
 
 def _bench(*extra: str, timeout: int = 500) -> dict:
     cmd = [sys.executable, "-u", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr=127.0.0.1", f"--master-port={_free_port()}", "bench.py", "--gpus", "2",
+           "--master-addr=127.0.0.1", f"--master-port={_free_port()}", "bench.py", "--full", "--gpus", "2",
            "--no-cpu-baseline", "--dist-backend", "gloo", *extra]
     env = dict(os.environ, PT_BENCH_SHARE_GPU="1", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
@@ -106,8 +106,8 @@ def test_one_gpu_validate_and_tile_check(gpu):
     the table scene kernel's throughput on the line."""
     # (32 spp: enough samples per step for the binned pipeline, whose
     # solo-pipeline run used to overwrite the image)
-    cmd = [sys.executable, "-u", "bench.py", "--no-cpu-baseline", "--width", "480", "--height", "272", "--spp", "32",
-           "--steps", "2", "--warmup", "1", "--validate"]
+    cmd = [sys.executable, "-u", "bench.py", "--full", "--no-cpu-baseline", "--width", "480", "--height", "272",
+           "--spp", "32", "--steps", "2", "--warmup", "1", "--validate"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -123,6 +123,54 @@ def test_one_gpu_validate_and_tile_check(gpu):
     assert tk["table_kernel_meanwhile"] is True and tk["tier_active_after"] is True
     assert tk["tier_compile_s"] > 0.1 and tk["tier_up_s"] >= tk["tier_compile_s"] and 1 <= tk["edit_ulps"] < 4096
     assert out["valid"] is True and out["schedule"]["bin_table"]["slots"] == 4096
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_is_lean_and_dumps_its_image(gpu, tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the
+    other legs', and --dump-outputs writes the image of the last timed step:
+    bit for bit the one-context render of every frame the run dispatched,
+    its non-finite channels as 0 and listed in nonfinite.npy."""
+    import numpy as np
+
+    from compute_path_tracer_amd import _native as N
+    from compute_path_tracer_amd import scenes
+    from compute_path_tracer_amd.path_tracer import PathTracer
+    from compute_path_tracer_amd.sdf_editor import CompData
+
+    w, h, spp = 480, 272, 32
+    cmd = [sys.executable, "-u", "bench.py", "--gpus", "1", "--width", str(w), "--height", str(h), "--spp", str(spp),
+           "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["valid"] is True and out["n_gpus"] == 1 and out["steps"] == 2
+    assert out["unit"] == "Msamples/sec" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(w * h * spp / (out["ms_per_step"] * 1e-3) / 1e6, rel=1e-2)
+    for k in ("roofline", "hbm", "work", "tile_check", "table_kernel", "cpu_baseline", "display", "host_readback"):
+        assert k not in out, k
+    got = np.load(tmp_path / "image.npy")
+    assert got.dtype == np.float32 and got.shape == (h, w, 4) and out["outputs"]["image"]["sampled"] is False
+    prog = scenes.c3_graph32().compile(CompData())
+    pt = PathTracer(w, h, prog, settings=N.Settings(debug=0, bounces=8, scale=1.0, fov=1.0, aabb=0))
+    try:
+        pt.dispatch(N.Constants(time=0.0, frame=1, aspect=float(np.float32(w) / np.float32(h)), last_clear=1), 3 * spp)
+        want = pt.read_image()
+    finally:
+        pt.close()
+    # finite files: a non-finite channel of the render is 0 in image.npy and a row of nonfinite.npy
+    nf = np.load(tmp_path / "nonfinite.npy")
+    assert np.isfinite(got).all() and np.isfinite(nf).all() and out["outputs"]["nonfinite"]["count"] == len(nf)
+    bad = np.flatnonzero(~np.isfinite(want.reshape(-1)))
+    assert np.array_equal(nf[:, 0].astype(np.int64), bad)
+    assert np.array_equal(nf[:, 1] == 1.0, np.isnan(want.reshape(-1)[bad]))
+    clean = want.copy()
+    clean.reshape(-1)[bad] = 0.0
+    assert np.array_equal(got.view(np.uint32), clean.view(np.uint32))
 
 
 @pytest.mark.timeout(600)
@@ -143,7 +191,7 @@ def test_bench_gpus_flag_launches_the_ranks(gpu):
     (torch.distributed.run as a child process) and the line says so: n_gpus
     2, the tile split bit-exact against a one-context render (VERDICT r03:
     --gpus was parsed and ignored)."""
-    cmd = [sys.executable, "-u", "bench.py", "--gpus", "2", "--no-cpu-baseline", "--dist-backend", "gloo",
+    cmd = [sys.executable, "-u", "bench.py", "--full", "--gpus", "2", "--no-cpu-baseline", "--dist-backend", "gloo",
            "--width", "480", "--height", "272", "--spp", "4", "--steps", "2", "--warmup", "1", "--validate"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(PT_BENCH_SHARE_GPU="1", OMP_NUM_THREADS="4")
