@@ -49,6 +49,7 @@ SYMBOLS = (
     "pt_destroy", "pt_abi_version", "pt_device_math", "pt_check_sqrt_exhaustive", "pt_check_div_exhaustive",
     "pt_check_div_random", "pt_check_box_random", "pt_check_div_k", "pt_display", "pt_write_accum",
     "pt_compile_scene_keyed", "pt_save_rgba8", "pt_comm_size", "pt_traffic_probe", "pt_scene_kernel_source",
+    "pt_set_camera", "pt_get_camera",
 )
 PT_MATH = {"max": 0, "min": 1, "sqrt": 2, "sqrtf": 3, "sin": 4, "cos": 5, "div": 6, "fma": 7}
 
@@ -63,6 +64,14 @@ class Settings(Structure):
     """== ``Settings`` UBO (path_tracer.rs:157-163); defaults match the reference sliders."""
 
     _fields_ = [("debug", c_int32), ("bounces", c_int32), ("scale", c_float), ("fov", c_float), ("aabb", c_int32)]
+
+
+class Camera(Structure):
+    """pt_camera: pose and lens of ``pt_set_camera`` (new; the reference's
+    view is fixed at origin (0, 0, -3) with the identity basis)."""
+
+    _fields_ = [("origin", c_float * 3), ("right", c_float * 3), ("up", c_float * 3), ("forward", c_float * 3),
+                ("aperture", c_float), ("focus", c_float)]
 
 
 class SceneNode(Structure):
@@ -99,6 +108,7 @@ class Aabb(Structure):
 
 
 assert ctypes.sizeof(Constants) == 16 and ctypes.sizeof(Settings) == 20
+assert ctypes.sizeof(Camera) == 56
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
 
@@ -133,6 +143,8 @@ def lib() -> ctypes.CDLL:
         "pt_set_program": (c_int, [ctx, POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, c_uint32]),
         "pt_set_data": (c_int, [ctx, POINTER(c_float), c_uint32]),
         "pt_set_tiles": (c_int, [ctx, c_uint32, c_uint32]),
+        "pt_set_camera": (c_int, [ctx, POINTER(Camera)]),
+        "pt_get_camera": (c_int, [ctx, POINTER(Camera), POINTER(c_int)]),
         "pt_dispatch": (c_int, [ctx, POINTER(Constants), POINTER(Settings), c_uint32]),
         "pt_read_accum": (c_int, [ctx, POINTER(c_float), c_size_t]),
         "pt_accum_device_ptr": (c_int, [ctx, POINTER(c_void_p), POINTER(c_size_t)]),

@@ -373,8 +373,8 @@ __device__ __forceinline__ uint32_t colour_slot(uint32_t frames, uint32_t f, uin
 
 // gen: camera ray + bounds() of every (frame, pixel) of the chunk
 // (MapBounds<Map>: the generic box loop, or the scene kernels' straight-line
-// slab tests).
-template <class Map, bool ST>
+// slab tests).  CAM: the cameras this instance serves (pt_path.h PT_CAMK_*).
+template <class Map, bool ST, int CAM = PT_CAMK_ANY>
 __device__ __forceinline__ void bin_gen_body(const PtPass &P) {
     __shared__ uint32_t lh[PT_BINS];
     hist_zero(lh);
@@ -396,7 +396,8 @@ __device__ __forceinline__ void bin_gen_body(const PtPass &P) {
         }
         uint32_t rng;
         pt_f3 ro, rd;
-        camera_ray(x, y, int32_t(uint32_t(L.frame0) + f), L.width, L.height, L.aspect, L.fov, rng, ro, rd);
+        camera_ray<CAM>(x, y, int32_t(uint32_t(L.frame0) + f), L.width, L.height, L.aspect, L.fov, L.cam_mode, L.cam,
+                        rng, ro, rd);
         st.add(PT_ST_SAMPLES);
         const uint4 m = MapBounds<Map>::template mask<ST>(L, ro, rd, st);
         const BinProbe bp = P.gen_order ? BinProbe{0u, 0ull, 0ull} : bin_probe(P, m);  // (before the stores)
@@ -430,7 +431,9 @@ __device__ __forceinline__ void bin_gen_body(const PtPass &P) {
 // tap_bound, carried in the quad) lets each tap drop every shape that
 // provably lies farther away.  TAPS = true: the hit records
 // of P.rout, shaded and replaced in place by the next rays.
-template <class Map, bool ST, bool TAPS>
+// CAM: the cameras whose rays shade pass 0 can make again (gen_norec;
+// pt_path.h PT_CAMK_*).
+template <class Map, bool ST, bool TAPS, int CAM = PT_CAMK_ANY>
 __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
     __shared__ uint32_t lh[PT_BINS];
     // the scene kernels' material table (MapMats<Map>::n entries) staged in
@@ -572,7 +575,9 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
                 pixel_of(rk, nr, tx, pl, x, y);
                 uint32_t rg;
                 pt_f3 o, d;
-                camera_ray(x, y, int32_t(uint32_t(L.frame0) + f), cw, chh, ca, cf, rg, o, d);
+                // (the camera itself straight from the launch block: only a
+                // posed camera's path reads it)
+                camera_ray<CAM>(x, y, int32_t(uint32_t(L.frame0) + f), cw, chh, ca, cf, L.cam_mode, L.cam, rg, o, d);
                 q0 = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
                 q1 = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(1.0f), __float_as_uint(1.0f));
                 q2 = make_uint4(__float_as_uint(1.0f), rg, colour_slot(nf, f, pl), i);
@@ -703,8 +708,9 @@ __device__ __forceinline__ void bin_scatter_body(const PtPass &P) {
 // window is one pixel over 64 frames) -- what gen would have written
 // (bin_gen_body), with all 64 lanes at once, and, for scenes of more than 32
 // check[] entries, stored to its slot for the shade pass -- so the chunk
-// needs no gen pass.
-template <class Map, bool ST, bool TAPS = true, bool GEN = false>
+// needs no gen pass.  CAM: the cameras whose rays a GEN instance makes
+// (pt_path.h PT_CAMK_*).
+template <class Map, bool ST, bool TAPS = true, bool GEN = false, int CAM = PT_CAMK_ANY>
 __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
     // the staged window, once its loads have landed: [part][lane], so a
     // refill reads a ray with 4 ds_read_b128 instead of 16 cross-lane moves
@@ -793,7 +799,8 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
             // the persistent loop, held a register there and spilled)
             float fov = L.fov;
             __asm__ volatile("" : "+v"(fov));
-            camera_ray(x, y, int32_t(uint32_t(L.frame0) + f), L.width, L.height, L.aspect, fov, rg, o, d);
+            camera_ray<CAM>(x, y, int32_t(uint32_t(L.frame0) + f), L.width, L.height, L.aspect, fov, L.cam_mode, L.cam,
+                            rg, o, d);
             st.add(PT_ST_SAMPLES);
             // the boxes no camera ray of the window can hit (every lane of a
             // full window is here, as the skip's wave reductions need)

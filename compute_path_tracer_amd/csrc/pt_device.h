@@ -128,7 +128,13 @@ struct PtLaunch {
     int32_t shade_batch;     // wavefront kernel: shade when >= this many lanes wait
     int32_t fast_bounds;     // every box coordinate passes pt_div_coord_ok (reciprocal slab divisions allowed)
     float bound_k;           // map() bound margin: the scene's transform-chain magnitude (NaN: no bound; pt_bound_k)
+    int32_t cam_mode;        // PT_CAM_*: which camera camera_ray (pt_path.h) applies
+    pt_camera cam;           // pt_set_camera's pose and lens (unused with PT_CAM_DEFAULT)
 };
+
+#define PT_CAM_DEFAULT 0  // the reference's fixed view: origin (0, 0, -3), looking down +z
+#define PT_CAM_PINHOLE 1  // posed pinhole (pt_camera with aperture 0)
+#define PT_CAM_LENS 2     // posed thin lens (aperture > 0)
 
 #define PT_KERNEL_AUTO 0
 #define PT_KERNEL_SIMPLE 1     // one path per lane, reference loop structure

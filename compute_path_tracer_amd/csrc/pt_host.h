@@ -38,6 +38,9 @@ struct PtJitModule {
     hipFunction_t gen = nullptr;  // camera rays + the scene's straight-line bounds()
     hipFunction_t gen_stats = nullptr;
     hipFunction_t trace_g = nullptr;  // first pass with its own camera rays (PtPass gen_trace)
+    // the kernels that make camera rays, built for a posed camera (pt_set_camera; pt_path.h PT_CAMK_POSED):
+    // gen pass, first pass, shade pass 0 -- the ones above serve the fixed camera only
+    hipFunction_t gen_c = nullptr, trace_gc = nullptr, shade_tc = nullptr;
     std::string key;  // generated source
 };
 

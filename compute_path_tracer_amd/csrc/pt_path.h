@@ -11,10 +11,28 @@ namespace pt {
 
 enum : int { ST_FREE = 0, ST_BOUNDS = 1, ST_MARCH = 2, ST_NORMAL = 3, ST_SHADE = 4 };
 
+// Which cameras a kernel instance serves (camera_ray's CAM): the first binned
+// pass, shade pass 0 and the gen pass of the scene kernels sit at their
+// register budget with the fixed camera's origin folded into their code as
+// constants, so they are built once for the fixed camera alone -- the code
+// they always had -- and once for a posed one, and the host launches the one
+// that matches (pt_runtime.hip).  Every other kernel branches on the launch
+// block's cam_mode, which is wave-uniform.
+#define PT_CAMK_ANY (-1)   // branch on cam_mode at run time
+#define PT_CAMK_FIXED 0    // PT_CAM_DEFAULT only
+#define PT_CAMK_POSED 1    // PT_CAM_PINHOLE / PT_CAM_LENS only
+
 // Camera ray of pixel (x, y) in frame `frame`: gen_rng, sub-pixel jitter,
-// calc_uv and the pinhole camera (test_compute.glsl:224-235).
+// calc_uv and the camera.  PT_CAM_DEFAULT: the reference's fixed pinhole
+// (test_compute.glsl:224-235), in its own code: the general formula's
+// ux * 1 + uy * 0 would turn a -0 into +0.  PT_CAM_PINHOLE / PT_CAM_LENS: the
+// pose and lens of pt_set_camera, read from the launch block
+// where they are used -- kernel arguments in scalar registers, never per-lane
+// state.  The lens draws its two numbers directly after the jitter's, and
+// the rng it leaves is the one the path goes on with.
+template <int CAM = PT_CAMK_ANY>
 __device__ __forceinline__ void camera_ray(int x, int y, int32_t frame, int width, int height, float aspect, float fov,
-                                           uint32_t &rng, pt_f3 &ro, pt_f3 &rd) {
+                                           int cam_mode, const pt_camera &cam, uint32_t &rng, pt_f3 &ro, pt_f3 &rd) {
     rng = pt_gen_rng(x, y, frame, width, height);
     float jx = pt_random01(rng);
     float jy = pt_random01(rng);
@@ -24,8 +42,31 @@ __device__ __forceinline__ void camera_ray(int x, int y, int32_t frame, int widt
     ux = ux * 2.0f - 1.0f;
     uy = uy * 2.0f - 1.0f;
     ux *= aspect;
-    rd = pt_normalize(pt_f3{ux, uy, fov});
-    ro = pt_f3{0.0f, 0.0f, -3.0f};
+    if (CAM == PT_CAMK_FIXED || (CAM == PT_CAMK_ANY && cam_mode == PT_CAM_DEFAULT)) {
+        rd = pt_normalize(pt_f3{ux, uy, fov});
+        ro = pt_f3{0.0f, 0.0f, -3.0f};
+        return;
+    }
+    const float *org = cam.origin, *right = cam.right, *up = cam.up, *fwd = cam.forward;
+    rd = pt_normalize(pt_f3{(right[0] * ux + up[0] * uy) + fwd[0] * fov, (right[1] * ux + up[1] * uy) + fwd[1] * fov,
+                            (right[2] * ux + up[2] * uy) + fwd[2] * fov});
+    ro = pt_f3{org[0], org[1], org[2]};
+    if (cam_mode == PT_CAM_LENS) {
+        // a point of the lens disc (radius aperture, spanned by right / up)
+        // aimed at the pinhole ray's point at distance focus
+        const float aperture = cam.aperture, focus = cam.focus;
+        const float u1 = pt_random01(rng);
+        const float u2 = pt_random01(rng);
+        const float r = pt_sqrt(u1) * aperture;
+        const float a = u2 * kPi2;
+        float sa, ca;
+        pt_sincos(a, sa, ca);
+        const float lx = r * ca, ly = r * sa;
+        const pt_f3 pf{ro.x + rd.x * focus, ro.y + rd.y * focus, ro.z + rd.z * focus};
+        ro = pt_f3{(ro.x + right[0] * lx) + up[0] * ly, (ro.y + right[1] * lx) + up[1] * ly,
+                   (ro.z + right[2] * lx) + up[2] * ly};
+        rd = pt_normalize(pt_f3{pf.x - ro.x, pf.y - ro.y, pf.z - ro.z});
+    }
 }
 
 // bounds(): one box's slab test, intersectAABB + bool_hit (aabb.glsl:21-33),

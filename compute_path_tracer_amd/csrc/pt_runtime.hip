@@ -43,6 +43,11 @@ struct JitBuild {
     int from = kJitCompiled;
 };
 
+static_assert(sizeof(pt_camera) == 14 * 4, "pt_camera layout");
+// the reference's fixed view as a pt_camera (what pt_get_camera reports for it)
+static const pt_camera kDefaultCamera = {{0.0f, 0.0f, -3.0f}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f},
+                                         {0.0f, 0.0f, 1.0f}, 0.0f, 1.0f};
+
 struct pt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -62,6 +67,9 @@ struct pt_ctx {
     size_t cap_nodes = 0, cap_aabbs = 0, cap_mats = 0;
     unsigned long long *d_stats = nullptr;  // 2 x PT_ST_COUNT (second half: the shade pass's normal taps)
     unsigned long long tap_stats[PT_ST_COUNT] = {};  // last pt_dispatch_stats: the shade-pass taps' share
+    // camera (pt_set_camera); cam_mode PT_CAM_DEFAULT: the reference's fixed view
+    int cam_mode = PT_CAM_DEFAULT;
+    pt_camera cam = kDefaultCamera;
     // tiles
     uint32_t rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;
@@ -627,6 +635,32 @@ int pt_set_tiles(pt_ctx *c, uint32_t rank, uint32_t nranks) {
     return pt_resize_clear(c, c->width, c->height);
 }
 
+int pt_set_camera(pt_ctx *c, const pt_camera *cam) {
+    if (!c) return PT_ERR_INVALID;
+    if (!cam) {
+        c->cam_mode = PT_CAM_DEFAULT;
+        c->cam = kDefaultCamera;
+        return PT_OK;
+    }
+    float v[14];
+    std::memcpy(v, cam, sizeof v);
+    for (float f : v)
+        if (!std::isfinite(f)) return fail(c, PT_ERR_INVALID, "camera field is not finite");
+    if (cam->aperture < 0.0f) return fail(c, PT_ERR_INVALID, "camera aperture must be >= 0");
+    if (cam->aperture > 0.0f && !(cam->focus > 0.0f))
+        return fail(c, PT_ERR_INVALID, "camera focus must be > 0 with an aperture");
+    c->cam = *cam;
+    c->cam_mode = cam->aperture > 0.0f ? PT_CAM_LENS : PT_CAM_PINHOLE;
+    return PT_OK;
+}
+
+int pt_get_camera(const pt_ctx *c, pt_camera *out, int *is_default) {
+    if (!c) return PT_ERR_INVALID;
+    if (out) *out = c->cam;
+    if (is_default) *is_default = c->cam_mode == PT_CAM_DEFAULT ? 1 : 0;
+    return PT_OK;
+}
+
 // ---- binned pipeline (pt_binned.h) -------------------------------------------
 // per sample of a chunk: two ray buffers, hit quad, bin key, binned slot,
 // colour (+ the high mask words and hits' high check[] words of scenes with
@@ -853,10 +887,13 @@ static int launch_binned(pt_ctx *c, PtLaunch &L, bool stats) {
     const unsigned trace_grid = cu * unsigned(std::max(1, per_cu));
     // the first pass's kernel may have been rebuilt at 7 waves on its own
     // (pt_jit_compile_source): the same one-slot-per-SIMD rule on its occupancy
+    // (a posed camera, pt_set_camera, takes the builds made for it: pt_host.h)
+    const bool posed = L.cam_mode != PT_CAM_DEFAULT;
+    const hipFunction_t trace_g = !jit ? nullptr : (posed ? jm->trace_gc : jm->trace_g);
     unsigned trace_g_grid = trace_grid;
-    if (jit && jm->trace_g) {
+    if (trace_g) {
         int g = 0;
-        HIPCHK(c, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&g, jm->trace_g, 64, 0));
+        HIPCHK(c, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&g, trace_g, 64, 0));
         if (g > 8) g = std::min(g - 4, 28);
         if (g > 0 && g < per_cu) trace_g_grid = cu * unsigned(g);
     }
@@ -941,15 +978,16 @@ static int launch_binned(pt_ctx *c, PtLaunch &L, bool stats) {
         // scene's gen kernel (straight-line bounds(): +1.4 % over the AOT one)
         if (!stats) c->gen_trace_used = c->gen_norec_used = 0;
         for (int i = 0; i < nl; ++i) {
-            if (P[i].gen_order && jit && taps_shade && !stats && jm->trace_g) {
+            if (P[i].gen_order && jit && taps_shade && !stats && trace_g) {
                 P[i].gen_trace = 1;
                 P[i].gen_norec = c->n_check <= 32 ? 1 : 0;  // (the check[] bits ride in the hit quad)
                 c->gen_trace_used = 1;
                 c->gen_norec_used = P[i].gen_norec;
             } else if (jit) {
                 void *args[] = {&P[i]};
-                HIPCHK(c, hipModuleLaunchKernel(stats ? jm->gen_stats : jm->gen, item_grid(size_t(P[i].n_src_const)), 1,
-                                                1, PT_BIN_BLOCK, 1, 1, 0, c->lane[i].stream, args, nullptr));
+                const hipFunction_t f = stats ? jm->gen_stats : (posed ? jm->gen_c : jm->gen);
+                HIPCHK(c, hipModuleLaunchKernel(f, item_grid(size_t(P[i].n_src_const)), 1, 1, PT_BIN_BLOCK, 1, 1, 0,
+                                                c->lane[i].stream, args, nullptr));
             } else {
                 pt_launch_bin(PtBinStage::Gen, P[i], stats, item_grid(size_t(P[i].n_src_const)), c->lane[i].stream);
                 HIPCHK(c, hipGetLastError());
@@ -968,8 +1006,10 @@ static int launch_binned(pt_ctx *c, PtLaunch &L, bool stats) {
             if (!stats) HIPCHK(c, record_event(c->slog, c->lane[i].stream));
             if (taps_shade) {
                 void *args[] = {&S};
-                HIPCHK(c, hipModuleLaunchKernel(stats ? jm->shade_t_stats : jm->shade_t, shade_grid, 1, 1, PT_BIN_BLOCK,
-                                                1, 1, 0, c->lane[i].stream, args, nullptr));
+                // (shade pass 0 without ray records makes the camera rays again)
+                const hipFunction_t f = stats ? jm->shade_t_stats : (posed && S.gen_norec ? jm->shade_tc : jm->shade_t);
+                HIPCHK(c, hipModuleLaunchKernel(f, shade_grid, 1, 1, PT_BIN_BLOCK, 1, 1, 0, c->lane[i].stream, args,
+                                                nullptr));
             } else {
                 pt_launch_bin(PtBinStage::Shade, S, stats, shade_grid, c->lane[i].stream);
                 HIPCHK(c, hipGetLastError());
@@ -999,7 +1039,7 @@ static int launch_binned(pt_ctx *c, PtLaunch &L, bool stats) {
                 if (!stats) HIPCHK(c, record_event(c->tlog, l.stream));
                 if (jit) {
                     void *args[] = {&p};
-                    HIPCHK(c, hipModuleLaunchKernel(gt ? jm->trace_g : jf, gt ? trace_g_grid : trace_grid, 1, 1, 64, 1,
+                    HIPCHK(c, hipModuleLaunchKernel(gt ? trace_g : jf, gt ? trace_g_grid : trace_grid, 1, 1, 64, 1,
                                                     1, 0, l.stream, args,
                                                     nullptr));
                 } else {
@@ -1085,6 +1125,8 @@ static int make_launch(pt_ctx *c, const pt_constants *k, const pt_settings *s, u
         L.kernel = work < 134217728.0 ? PT_KERNEL_WAVEFRONT : PT_KERNEL_BINNED;
     }
     L.shade_batch = c->shade_batch;
+    L.cam_mode = c->cam_mode;
+    L.cam = c->cam;
     return PT_OK;
 }
 

@@ -10,7 +10,10 @@ id travels over the torch process group.  The reference has no multi-GPU path
 
 The orchestration is backend-agnostic: anything with ``set_tiles``,
 ``dispatch``, ``comm_unique_id``/``comm_init`` and ``reduce``/``read_reduced``
-(PathTracer on the GPU) can be driven by :class:`TileSplitRender`.
+(PathTracer on the GPU) can be driven by :class:`TileSplitRender`.  It
+receives a configured renderer: a camera (``PathTracer.set_camera`` /
+``look_at``) is set on each rank's renderer, the same on every rank, before
+the render.
 """
 from __future__ import annotations
 

@@ -24,6 +24,45 @@ def default_settings() -> N.Settings:
     return N.Settings(debug=1, bounces=8, scale=1.0, fov=1.0, aabb=0)
 
 
+def look_at_camera(eye, target, up=(0.0, 1.0, 0.0), aperture: float = 0.0, focus: Optional[float] = None) -> N.Camera:
+    """The ``pt_camera`` at ``eye`` looking at ``target``, in float32 steps:
+    forward = normalize(target - eye), right = normalize(cross(up, forward)),
+    the camera's up = cross(forward, right) (oriented as the reference's +x
+    right / +y up / +z forward view); ``focus`` defaults to |target - eye|.
+    ``look_at_camera((0, 0, -3), (0, 0, 0))`` is the reference's camera.  Host
+    arithmetic only (no context)."""
+    F = np.float32
+
+    def vec(v, name):
+        a = np.asarray(v, dtype=np.float32)
+        if a.shape != (3,) or not np.isfinite(a).all():
+            raise ValueError(f"{name} must be three finite numbers, got {v!r}")
+        return a
+
+    def cross(a, b):
+        return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]], dtype=F)
+
+    def length(a):
+        return np.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
+
+    e, t, u = vec(eye, "eye"), vec(target, "target"), vec(up, "up")
+    d = t - e
+    dist = length(d)
+    if not dist > 0:
+        raise ValueError("eye and target coincide")
+    fwd = d / dist
+    r = cross(u, fwd)
+    rl = length(r)
+    if not rl > F(1e-6) * length(u):
+        raise ValueError(f"up {up!r} is parallel to the view direction")
+    right = r / rl
+    cup = cross(fwd, right)
+    cam = N.Camera(aperture=float(aperture), focus=float(dist if focus is None else focus))
+    for k in range(3):
+        cam.origin[k], cam.right[k], cam.up[k], cam.forward[k] = e[k], right[k], cup[k], fwd[k]
+    return cam
+
+
 class PathTracer:
     def __init__(self, width: int, height: int, program: Optional[Program] = None, data: Optional[np.ndarray] = None,
                  device: int = 0, settings: Optional[N.Settings] = None, options: Optional[dict] = None):
@@ -150,6 +189,42 @@ class PathTracer:
 
     def set_tiles(self, rank: int, nranks: int) -> None:
         self._chk("pt_set_tiles", self._L.pt_set_tiles(self._ctx, rank, nranks))
+
+    # -- camera (new: the reference's view is fixed) ------------------------
+    def _set_camera(self, cam: Optional[N.Camera]) -> None:
+        self._chk("pt_set_camera", self._L.pt_set_camera(self._ctx, ctypes.byref(cam) if cam is not None else None))
+        self.changed = True  # the next update() clears the image, as for a settings change
+
+    def set_camera(self, origin, right, up, forward, aperture: float = 0.0, focus: float = 1.0) -> N.Camera:
+        """pt_set_camera: a primary ray leaves ``origin`` along
+        normalize(right * ux + up * uy + forward * fov); ``aperture`` > 0 is a
+        thin lens of that radius focused at distance ``focus``.  The basis is
+        used as given (look_at builds an orthonormal one)."""
+        cam = N.Camera(aperture=float(aperture), focus=float(focus))
+        for name, v in (("origin", origin), ("right", right), ("up", up), ("forward", forward)):
+            if len(v) != 3:
+                raise ValueError(f"{name} must have three components, got {v!r}")
+            for k in range(3):
+                getattr(cam, name)[k] = float(v[k])
+        self._set_camera(cam)
+        return cam
+
+    def look_at(self, eye, target, up=(0.0, 1.0, 0.0), aperture: float = 0.0, focus: Optional[float] = None) -> N.Camera:
+        """Place the camera at ``eye`` looking at ``target`` (look_at_camera);
+        returns the Camera it set."""
+        cam = look_at_camera(eye, target, up, aperture, focus)
+        self._set_camera(cam)
+        return cam
+
+    def reset_camera(self) -> None:
+        """Back to the reference's fixed camera."""
+        self._set_camera(None)
+
+    def get_camera(self):
+        """(Camera in force, True when it is the reference's fixed one)."""
+        cam, dflt = N.Camera(), ctypes.c_int()
+        self._chk("pt_get_camera", self._L.pt_get_camera(self._ctx, ctypes.byref(cam), ctypes.byref(dflt)))
+        return cam, bool(dflt.value)
 
     def clear(self) -> None:
         self._chk("pt_resize_clear", self._L.pt_resize_clear(self._ctx, self.size[0], self.size[1]))

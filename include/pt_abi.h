@@ -168,6 +168,31 @@ int pt_set_data(pt_ctx *ctx, const float *data, uint32_t n);
 /* Multi-GPU tile ownership (new): 8x8 tile t is rendered iff t % nranks == rank.
  * Clears the image (non-owned texels stay exactly 0). */
 int pt_set_tiles(pt_ctx *ctx, uint32_t rank, uint32_t nranks);
+/* Camera pose and lens (new; the reference's view is fixed, test_compute.glsl:
+ * 232-235).  With ux, uy the jittered, aspect-scaled screen coordinates the
+ * reference forms, a primary ray leaves `origin` along
+ * normalize(right * ux + up * uy + forward * fov); the reference's camera is
+ * origin (0, 0, -3) with the identity basis.  aperture > 0 is a thin lens of
+ * that radius: the ray starts at a uniformly drawn point of the lens disc
+ * (spanned by right and up) and passes through the pinhole ray's point at
+ * distance `focus` (DESIGN.md 3.24 has the f32 steps and the draw order).
+ * The basis is used as given: it is not checked for orthonormality, and a
+ * skewed or scaled one shears or zooms the picture. */
+typedef struct {            /* 56 bytes, 14 floats */
+    float origin[3];
+    float right[3], up[3], forward[3];   /* camera basis in world space */
+    float aperture;         /* lens radius; 0 = pinhole */
+    float focus;            /* distance along the ray to the in-focus point; used iff aperture > 0 */
+} pt_camera;
+/* cam == NULL: back to the reference's fixed camera.  PT_ERR_INVALID (the
+ * previous camera stays in force) when a field is not finite, aperture < 0,
+ * or aperture > 0 with focus <= 0.  Takes effect at the next pt_dispatch /
+ * pt_dispatch_stats; does not clear the image (the caller does, as for a
+ * settings change). */
+int pt_set_camera(pt_ctx *ctx, const pt_camera *cam);
+/* The camera in force; *is_default = 1 when it is the reference's fixed one
+ * (*out then holds its pose).  Either output may be NULL. */
+int pt_get_camera(const pt_ctx *ctx, pt_camera *out, int *is_default);
 /* == `spp` successive (PathTracer::update, compute_pass) pairs: frame j uses
  * frame = c->frame + j and last_clear = c->last_clear + j (path_tracer.rs:
  * 110-111).  Asynchronous, ordered on the context's HIP stream. */
