@@ -49,7 +49,7 @@ SYMBOLS = (
     "pt_destroy", "pt_abi_version", "pt_device_math", "pt_check_sqrt_exhaustive", "pt_check_div_exhaustive",
     "pt_check_div_random", "pt_check_box_random", "pt_check_div_k", "pt_display", "pt_write_accum",
     "pt_compile_scene_keyed", "pt_save_rgba8", "pt_comm_size", "pt_traffic_probe", "pt_scene_kernel_source",
-    "pt_set_camera", "pt_get_camera",
+    "pt_set_camera", "pt_get_camera", "pt_set_sky", "pt_get_sky",
 )
 PT_MATH = {"max": 0, "min": 1, "sqrt": 2, "sqrtf": 3, "sin": 4, "cos": 5, "div": 6, "fma": 7}
 
@@ -72,6 +72,14 @@ class Camera(Structure):
 
     _fields_ = [("origin", c_float * 3), ("right", c_float * 3), ("up", c_float * 3), ("forward", c_float * 3),
                 ("aperture", c_float), ("focus", c_float)]
+
+
+class Sky(Structure):
+    """pt_sky: gradient and sun of ``pt_set_sky`` (new; in the reference a ray
+    that leaves the scene adds nothing)."""
+
+    _fields_ = [("bottom", c_float * 3), ("top", c_float * 3), ("sun_dir", c_float * 3), ("sun_color", c_float * 3),
+                ("sun_cos", c_float)]
 
 
 class SceneNode(Structure):
@@ -108,7 +116,7 @@ class Aabb(Structure):
 
 
 assert ctypes.sizeof(Constants) == 16 and ctypes.sizeof(Settings) == 20
-assert ctypes.sizeof(Camera) == 56
+assert ctypes.sizeof(Camera) == 56 and ctypes.sizeof(Sky) == 52
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
 
@@ -145,6 +153,8 @@ def lib() -> ctypes.CDLL:
         "pt_set_tiles": (c_int, [ctx, c_uint32, c_uint32]),
         "pt_set_camera": (c_int, [ctx, POINTER(Camera)]),
         "pt_get_camera": (c_int, [ctx, POINTER(Camera), POINTER(c_int)]),
+        "pt_set_sky": (c_int, [ctx, POINTER(Sky)]),
+        "pt_get_sky": (c_int, [ctx, POINTER(Sky), POINTER(c_int)]),
         "pt_dispatch": (c_int, [ctx, POINTER(Constants), POINTER(Settings), c_uint32]),
         "pt_read_accum": (c_int, [ctx, POINTER(c_float), c_size_t]),
         "pt_accum_device_ptr": (c_int, [ctx, POINTER(c_void_p), POINTER(c_size_t)]),

@@ -16,6 +16,8 @@
 //           and handed to free lanes, which march and calc_normal them; a
 //           miss stores the path's colour, a hit writes a hit record to the
 //           other ray buffer at its binned position
+//   sky     (only with pt_set_sky) each miss of the trace pass adds the sky's
+//           radiance times the traced ray's throughput to its colour slot
 //   shade   shading + Russian roulette of every hit record, then bounds()
 //           mask + bin of each continuing ray (next pass)
 //   fold    each pixel mixes its frames' colours in frame order
@@ -56,7 +58,8 @@
 //                                        pixel; aux: a ray's own slot (its index
 //                                        in its buffer), a hit record's material
 //                                        index, or PT_AUX_MISS (a miss writes
-//                                        only this quad)
+//                                        only this quad, with the traced
+//                                        ray's slot in place of thr.z)
 //   q3 = ray: check[] bits 0..63 of the segment to trace (64..127: PtPass.mask_hi)
 //        hit record: (calc_normal's differences, 0)
 // With the taps in the shade pass (the scene kernels) the trace pass writes
@@ -844,7 +847,8 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
                     const pt_f3 c = final_color(L.debug, P.bounce, L.bounces, pt_f3{0.0f, 0.0f, 0.0f});
                     P.color[sid] = make_float4(c.x, c.y, c.z, 0.0f);
                 }
-                if constexpr (TAPS) P.rout[pos].q[2] = make_uint4(0u, 0u, sid, PT_AUX_MISS);
+                // (.x: the traced ray's slot, for the sky pass -- pt_kernel.hip pt_bin_sky_kernel)
+                if constexpr (TAPS) P.rout[pos].q[2] = make_uint4(slot, 0u, sid, PT_AUX_MISS);
                 else P.hq[pos] = make_uint4(0u, PT_AUX_MISS, 0u, slot);
                 if constexpr (GEN) P.color[sid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (no gen pass zeroed it)
             } else {

@@ -130,7 +130,12 @@ struct PtLaunch {
     float bound_k;           // map() bound margin: the scene's transform-chain magnitude (NaN: no bound; pt_bound_k)
     int32_t cam_mode;        // PT_CAM_*: which camera camera_ray (pt_path.h) applies
     pt_camera cam;           // pt_set_camera's pose and lens (unused with PT_CAM_DEFAULT)
+    int32_t sky_mode;        // PT_SKY_*: whether a segment that misses adds sky_radiance (pt_path.h); 0 with debug != 0
+    pt_sky sky;              // pt_set_sky's gradient and sun (unused with PT_SKY_OFF)
 };
+
+#define PT_SKY_OFF 0  // the reference's void: a miss adds nothing
+#define PT_SKY_ON 1   // gradient + sun (pt_sky)
 
 #define PT_CAM_DEFAULT 0  // the reference's fixed view: origin (0, 0, -3), looking down +z
 #define PT_CAM_PINHOLE 1  // posed pinhole (pt_camera with aperture 0)

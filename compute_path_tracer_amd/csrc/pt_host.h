@@ -15,6 +15,9 @@ void pt_launch_render(const PtLaunch &L, bool stats, hipStream_t stream);
 enum class PtBinStage { Gen, Shade, Scan, Scatter, Trace, Fold };
 void pt_launch_bin(PtBinStage stage, const PtPass &P, bool stats, unsigned grid, hipStream_t stream);
 int pt_bin_trace_blocks_per_cu(bool stats);  // occupancy of the interpreter trace kernel
+// the sky pass after a binned trace pass (pt_set_sky): P as that trace pass's shade pass takes it; quads: the
+// trace pass wrote hit quads (taps in the shade pass), not hit records
+void pt_launch_bin_sky(const PtPass &P, bool quads, unsigned grid, hipStream_t stream);
 void pt_launch_display(const float *img, uint32_t w, uint32_t h, int fmt, void *out, hipStream_t stream);
 
 // Expand (program, data[]) into the device tables (see pt_device.h).

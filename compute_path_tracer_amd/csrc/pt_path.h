@@ -69,6 +69,45 @@ __device__ __forceinline__ void camera_ray(int x, int y, int32_t frame, int widt
     }
 }
 
+// Radiance of the sky (pt_set_sky) along direction rd: the
+// vertical gradient, plus the sun's colour inside its disc.  f32, no
+// contraction, in this order.  The sky itself is read from the launch block
+// where it is used -- kernel arguments in scalar registers, never per-lane
+// state.
+__device__ __forceinline__ pt_f3 sky_radiance(const pt_sky &sky, const pt_f3 &rd) {
+    const float t = rd.y * 0.5f + 0.5f;
+    pt_f3 g{sky.bottom[0] + (sky.top[0] - sky.bottom[0]) * t, sky.bottom[1] + (sky.top[1] - sky.bottom[1]) * t,
+            sky.bottom[2] + (sky.top[2] - sky.bottom[2]) * t};
+    const float s = pt_dot(rd, pt_f3{sky.sun_dir[0], sky.sun_dir[1], sky.sun_dir[2]});
+    if (s >= sky.sun_cos) {
+        g.x = g.x + sky.sun_color[0];
+        g.y = g.y + sky.sun_color[1];
+        g.z = g.z + sky.sun_color[2];
+    }
+    return g;
+}
+
+// A segment that missed (CastRay's t > FP, test_compute.glsl:106) with a sky
+// set: ret += sky_radiance(rd) * thr before the path ends.  Behind the launch
+// block's sky_mode, which is wave-uniform (a scalar branch: without a sky the
+// lanes skip the whole term).  No rng draw.
+__device__ __forceinline__ void sky_miss(const PtLaunch &L, const pt_f3 &rd, const pt_f3 &thr, pt_f3 &ret) {
+    if (L.sky_mode == PT_SKY_OFF) return;
+    // (the sky's offset in the launch block through an empty asm: read as
+    // L.sky, the 13 loads are loop-invariant kernel arguments, the compiler
+    // hoists them out of the wave kernel's main loop, and their scalar
+    // registers, held across the whole body, cost the C3 scene kernel 9
+    // VGPRs of spills and one wave of occupancy -- with or without a sky.
+    // With an offset it cannot see, the loads stay inside this branch.)
+    uint32_t off = uint32_t(__builtin_offsetof(PtLaunch, sky));
+    __asm__ volatile("" : "+s"(off));
+    const pt_sky &sky = *reinterpret_cast<const pt_sky *>(reinterpret_cast<const char *>(&L) + off);
+    const pt_f3 g = sky_radiance(sky, rd);
+    ret.x = ret.x + g.x * thr.x;
+    ret.y = ret.y + g.y * thr.y;
+    ret.z = ret.z + g.z * thr.z;
+}
+
 // bounds(): one box's slab test, intersectAABB + bool_hit (aabb.glsl:21-33),
 // as the generated bounds() applies it per check[] entry.
 __device__ __forceinline__ bool ray_box(const PtAabb &bx, float ox, float oy, float oz, float dx, float dy, float dz) {

@@ -44,6 +44,7 @@ struct JitBuild {
 };
 
 static_assert(sizeof(pt_camera) == 14 * 4, "pt_camera layout");
+static_assert(sizeof(pt_sky) == 13 * 4, "pt_sky layout");
 // the reference's fixed view as a pt_camera (what pt_get_camera reports for it)
 static const pt_camera kDefaultCamera = {{0.0f, 0.0f, -3.0f}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f},
                                          {0.0f, 0.0f, 1.0f}, 0.0f, 1.0f};
@@ -70,6 +71,9 @@ struct pt_ctx {
     // camera (pt_set_camera); cam_mode PT_CAM_DEFAULT: the reference's fixed view
     int cam_mode = PT_CAM_DEFAULT;
     pt_camera cam = kDefaultCamera;
+    // sky (pt_set_sky); sky_mode PT_SKY_OFF: the reference's void
+    int sky_mode = PT_SKY_OFF;
+    pt_sky sky = {};
     // tiles
     uint32_t rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;
@@ -136,7 +140,7 @@ struct pt_ctx {
     struct EventLog {
         std::vector<hipEvent_t> ev;
         size_t used = 0;
-    } tlog, slog;
+    } tlog, slog, klog;  // (klog: the sky passes, pt_set_sky)
     // display pass output (device) and its timing
     void *d_display = nullptr;
     size_t cap_display = 0;
@@ -661,6 +665,33 @@ int pt_get_camera(const pt_ctx *c, pt_camera *out, int *is_default) {
     return PT_OK;
 }
 
+int pt_set_sky(pt_ctx *c, const pt_sky *sky) {
+    if (!c) return PT_ERR_INVALID;
+    if (!sky) {
+        c->sky_mode = PT_SKY_OFF;
+        c->sky = pt_sky{};
+        return PT_OK;
+    }
+    float v[13];
+    std::memcpy(v, sky, sizeof v);
+    for (float f : v)
+        if (!std::isfinite(f)) return fail(c, PT_ERR_INVALID, "sky field is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (sky->bottom[k] < 0.0f || sky->top[k] < 0.0f || sky->sun_color[k] < 0.0f)
+            return fail(c, PT_ERR_INVALID, "sky colour component must be >= 0");
+    if (sky->sun_cos < -1.0f || sky->sun_cos > 1.0f) return fail(c, PT_ERR_INVALID, "sky sun_cos must lie in [-1, 1]");
+    c->sky = *sky;
+    c->sky_mode = PT_SKY_ON;
+    return PT_OK;
+}
+
+int pt_get_sky(const pt_ctx *c, pt_sky *out, int *is_off) {
+    if (!c) return PT_ERR_INVALID;
+    if (out) *out = c->sky;
+    if (is_off) *is_off = c->sky_mode == PT_SKY_OFF ? 1 : 0;
+    return PT_OK;
+}
+
 // ---- binned pipeline (pt_binned.h) -------------------------------------------
 // per sample of a chunk: two ray buffers, hit quad, bin key, binned slot,
 // colour (+ the high mask words and hits' high check[] words of scenes with
@@ -1047,6 +1078,17 @@ static int launch_binned(pt_ctx *c, PtLaunch &L, bool stats) {
                     HIPCHK(c, hipGetLastError());
                 }
                 if (!stats) HIPCHK(c, record_event(c->tlog, l.stream));
+                // a sky (pt_set_sky): the misses of this trace pass take its radiance, before the
+                // shade pass of its hits (no sky, no launch; the instrumented run counts no work of
+                // this pass and writes no image, so it leaves the pass out)
+                if (L.sky_mode != PT_SKY_OFF && !stats) {
+                    PtPass K = p;
+                    K.n_src = p.ctrl;  // this trace pass's ray count
+                    HIPCHK(c, record_event(c->klog, l.stream));
+                    pt_launch_bin_sky(K, taps_shade, item_grid(k == 0 ? size_t(p.n_src_const) : c->bin_cap), l.stream);
+                    HIPCHK(c, hipGetLastError());
+                    HIPCHK(c, record_event(c->klog, l.stream));
+                }
             }
         }
         for (int i = 0; i < nl; ++i)  // the last bounce's hits end their paths
@@ -1127,6 +1169,9 @@ static int make_launch(pt_ctx *c, const pt_constants *k, const pt_settings *s, u
     L.shade_batch = c->shade_batch;
     L.cam_mode = c->cam_mode;
     L.cam = c->cam;
+    // (the debug views never add the sky: 1 and 2 do not path trace, 3 shows the segment count)
+    L.sky_mode = s->debug == 0 ? c->sky_mode : PT_SKY_OFF;
+    L.sky = c->sky;
     return PT_OK;
 }
 
@@ -1137,7 +1182,7 @@ int pt_dispatch(pt_ctx *c, const pt_constants *k, const pt_settings *s, uint32_t
     HIPCHK(c, hipSetDevice(c->device));
     jit_tier_poll(c, false);  // switch to the values-baked kernel once it is built
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    c->tlog.used = c->slog.used = 0;
+    c->tlog.used = c->slog.used = c->klog.used = 0;
     if (spp > 0 && L.n_tiles > 0) {
         // bound a single launch's length; chunks continue frame/last_clear.
         // The binned pipeline takes every frame at once: it splits by its own
@@ -1403,6 +1448,7 @@ int pt_get_option(pt_ctx *c, const char *key, double *value) {
     }
     else if (!std::strcmp(key, "trace_launches")) *value = double(c->tlog.used / 2);
     else if (!std::strcmp(key, "shade_launches")) *value = double(c->slog.used / 2);
+    else if (!std::strcmp(key, "sky_launches")) *value = double(c->klog.used / 2);
     else if (!std::strcmp(key, "display_ms")) {
         float ms = 0.0f;
         if (c->display_timed) HIPCHK(c, hipEventElapsedTime(&ms, c->dev0, c->dev1));
@@ -1410,6 +1456,7 @@ int pt_get_option(pt_ctx *c, const char *key, double *value) {
     }
     else if (!std::strcmp(key, "trace_ms")) HIPCHK(c, event_log_ms(c->tlog, value));  // summed over the trace passes
     else if (!std::strcmp(key, "shade_ms")) HIPCHK(c, event_log_ms(c->slog, value));  // summed over the shade passes
+    else if (!std::strcmp(key, "sky_ms")) HIPCHK(c, event_log_ms(c->klog, value));  // summed over the sky passes (pt_set_sky)
     else if (!std::strcmp(key, "bin_bytes")) *value = double(c->bin_cap) * double(c->n_lanes) * double(bin_bytes_per_sample(c));
     else if (!std::strcmp(key, "bin_lanes")) *value = double(c->bin_lanes);
     else if (!std::strcmp(key, "bin_table")) *value = double(c->bin_table);
@@ -1458,6 +1505,7 @@ void pt_destroy(pt_ctx *c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->tlog.ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->slog.ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->klog.ev) (void)hipEventDestroy(e);
     (void)hipFree(c->d_display);
     if (c->dev0) (void)hipEventDestroy(c->dev0);
     if (c->dev1) (void)hipEventDestroy(c->dev1);

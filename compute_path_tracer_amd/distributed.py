@@ -13,7 +13,8 @@ The orchestration is backend-agnostic: anything with ``set_tiles``,
 (PathTracer on the GPU) can be driven by :class:`TileSplitRender`.  It
 receives a configured renderer: a camera (``PathTracer.set_camera`` /
 ``look_at``) is set on each rank's renderer, the same on every rank, before
-the render.
+the render, and so is a sky (``PathTracer.set_sky``): both are per context,
+so nothing here changes with them.
 """
 from __future__ import annotations
 

@@ -63,6 +63,43 @@ def look_at_camera(eye, target, up=(0.0, 1.0, 0.0), aperture: float = 0.0, focus
     return cam
 
 
+def sky_light(bottom, top=None, sun_direction=None, sun_color=(0.0, 0.0, 0.0), sun_angle: float = 0.0) -> N.Sky:
+    """The ``pt_sky`` with radiance ``bottom`` looking straight down and
+    ``top`` straight up (default: ``bottom``, a uniform ambient light), and a
+    sun of radiance ``sun_color`` within ``sun_angle`` degrees of
+    ``sun_direction`` (towards the sun; normalised here in float32 steps, and
+    (0, 1, 0) without one): sun_cos = float32(cos(radians(sun_angle))).  Host
+    arithmetic only (no context)."""
+    F = np.float32
+
+    def vec(v, name):
+        a = np.asarray(v, dtype=np.float32)
+        if a.shape != (3,) or not np.isfinite(a).all():
+            raise ValueError(f"{name} must be three finite numbers, got {v!r}")
+        return a
+
+    def colour(v, name):
+        a = vec(v, name)
+        if (a < 0).any():
+            raise ValueError(f"{name} must not be negative, got {v!r}")
+        return a
+
+    b = colour(bottom, "bottom")
+    t = b if top is None else colour(top, "top")
+    sc = colour(sun_color, "sun_color")
+    d = vec((0.0, 1.0, 0.0) if sun_direction is None else sun_direction, "sun_direction")
+    dl = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    if not dl > 0:
+        raise ValueError("sun_direction is zero")
+    d = d / dl
+    if not 0.0 <= float(sun_angle) <= 180.0:
+        raise ValueError(f"sun_angle must lie in [0, 180] degrees, got {sun_angle!r}")
+    sky = N.Sky(sun_cos=float(F(np.cos(np.radians(float(sun_angle))))))
+    for k in range(3):
+        sky.bottom[k], sky.top[k], sky.sun_dir[k], sky.sun_color[k] = b[k], t[k], d[k], sc[k]
+    return sky
+
+
 class PathTracer:
     def __init__(self, width: int, height: int, program: Optional[Program] = None, data: Optional[np.ndarray] = None,
                  device: int = 0, settings: Optional[N.Settings] = None, options: Optional[dict] = None):
@@ -225,6 +262,30 @@ class PathTracer:
         cam, dflt = N.Camera(), ctypes.c_int()
         self._chk("pt_get_camera", self._L.pt_get_camera(self._ctx, ctypes.byref(cam), ctypes.byref(dflt)))
         return cam, bool(dflt.value)
+
+    # -- sky (new: in the reference a ray that leaves the scene adds nothing) --
+    def _set_sky(self, sky: Optional[N.Sky]) -> None:
+        self._chk("pt_set_sky", self._L.pt_set_sky(self._ctx, ctypes.byref(sky) if sky is not None else None))
+        self.changed = True  # the next update() clears the image, as for a settings change
+
+    def set_sky(self, bottom, top=None, sun_direction=None, sun_color=(0.0, 0.0, 0.0), sun_angle: float = 0.0) -> N.Sky:
+        """pt_set_sky: light for rays that leave the scene -- a vertical
+        gradient from ``bottom`` to ``top`` and a sun disc (sky_light's
+        arguments), or a ready ``Sky`` as the only argument, passed on as it
+        is.  Returns the Sky it set."""
+        sky = bottom if isinstance(bottom, N.Sky) else sky_light(bottom, top, sun_direction, sun_color, sun_angle)
+        self._set_sky(sky)
+        return sky
+
+    def clear_sky(self) -> None:
+        """Back to the reference's void: a ray that leaves the scene adds nothing."""
+        self._set_sky(None)
+
+    def get_sky(self):
+        """(Sky in force, True when none is set)."""
+        sky, off = N.Sky(), ctypes.c_int()
+        self._chk("pt_get_sky", self._L.pt_get_sky(self._ctx, ctypes.byref(sky), ctypes.byref(off)))
+        return sky, bool(off.value)
 
     def clear(self) -> None:
         self._chk("pt_resize_clear", self._L.pt_resize_clear(self._ctx, self.size[0], self.size[1]))

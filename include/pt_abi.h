@@ -193,6 +193,32 @@ int pt_set_camera(pt_ctx *ctx, const pt_camera *cam);
 /* The camera in force; *is_default = 1 when it is the reference's fixed one
  * (*out then holds its pose).  Either output may be NULL. */
 int pt_get_camera(const pt_ctx *ctx, pt_camera *out, int *is_default);
+/* Sky light (new; in the reference a ray that leaves the scene adds nothing,
+ * test_compute.glsl:106, and its AMBENT is never used).  With a sky set and
+ * debug == 0, a segment whose march misses (CastRay's t > FP) adds, before
+ * the path ends, g * throughput to the path's radiance, where for the
+ * segment's direction rd
+ *   t = rd.y * 0.5 + 0.5,  g = bottom + (top - bottom) * t,
+ *   g += sun_color  where dot(rd, sun_dir) >= sun_cos
+ * (DESIGN.md 3.25 has the f32 steps).  Paths that end by Russian roulette or
+ * at the bounce limit add nothing, no random number is drawn, and the debug
+ * views do not change. */
+typedef struct {            /* 52 bytes, 13 floats */
+    float bottom[3];        /* radiance looking straight down (rd.y = -1) */
+    float top[3];           /* radiance looking straight up   (rd.y = +1) */
+    float sun_dir[3];       /* towards the sun; used as given, not normalised */
+    float sun_color[3];     /* added where dot(rd, sun_dir) >= sun_cos; all 0 = no sun */
+    float sun_cos;
+} pt_sky;
+/* sky == NULL: off, the reference's void.  PT_ERR_INVALID (the previous sky
+ * stays in force) when a field is not finite, a colour component is negative
+ * or sun_cos lies outside [-1, 1].  Takes effect at the next pt_dispatch /
+ * pt_dispatch_stats; does not clear the image (the caller does, as for a
+ * settings change); survives pt_resize_clear, pt_set_program and pt_set_data. */
+int pt_set_sky(pt_ctx *ctx, const pt_sky *sky);
+/* The sky in force; *is_off = 1 when none is set (*out is then all zero).
+ * Either output may be NULL. */
+int pt_get_sky(const pt_ctx *ctx, pt_sky *out, int *is_off);
 /* == `spp` successive (PathTracer::update, compute_pass) pairs: frame j uses
  * frame = c->frame + j and last_clear = c->last_clear + j (path_tracer.rs:
  * 110-111).  Asynchronous, ordered on the context's HIP stream. */
@@ -283,7 +309,8 @@ int pt_set_option(pt_ctx *ctx, const char *key, int value);
  * pipeline), "bin_chunks" (chunks of the last binned dispatch), "bin_fallback"
  * (1: the chunk size came from the free memory), "trace_ms" / "trace_launches" (device time and count of the last
  * dispatch's binned trace passes, HIP events on each pipeline's stream),
- * "shade_ms" / "shade_launches" (the same for its shade passes), "display_ms"
+ * "shade_ms" / "shade_launches" (the same for its shade passes), "sky_ms" /
+ * "sky_launches" (the same for its sky passes, pt_set_sky; 0 without a sky), "display_ms"
  * (device time of the last pt_display's kernel), "gen_trace" / "gen_norec"
  * (the last timed binned dispatch's first pass made its own camera rays /
  * and stored no ray records for shade pass 0). */

@@ -1,0 +1,177 @@
+"""The sky on the CPU (no GPU): tests/skyref.py, the reference the GPU sky
+tests compare with, against the C oracle where the oracle can render (no
+sky), against the sky's formula on a scene where every ray misses, and the
+sky_light arithmetic of the Python mirror.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import pyref as P
+import skyref
+from compute_path_tracer_amd import scenes
+from oracle import oracle as O
+
+F = np.float32
+
+EYE, TARGET = (2.0, 1.5, -2.5), (0.0, 0.0, 0.0)  # the camera tests' pose
+LOOK = {"default": None, "pinhole": {}, "lens": {"aperture": 0.05, "focus": 3.0}}
+
+
+def _aspect(w, h):
+    return float(F(w) / F(h))
+
+
+def _sky_light(*args, **kw):
+    from compute_path_tracer_amd.path_tracer import sky_light  # host arithmetic: needs no context
+
+    return sky_light(*args, **kw)
+
+
+def _camera(kind):
+    from compute_path_tracer_amd.path_tracer import look_at_camera
+
+    return None if LOOK[kind] is None else look_at_camera(EYE, TARGET, **LOOK[kind])
+
+
+def _test_sky():
+    """The sky of every GPU test (tests/test_gpu_sky.py)."""
+    return _sky_light((0.9, 0.8, 0.7), (0.25, 0.45, 0.9), (0.4, 0.7, -0.6), (8.0, 7.0, 5.0), 30.0)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(name, w, h, spp, bounces, debug=0):
+    rows = scenes.SCENES[name]().rows()
+    a = _aspect(w, h)
+    img = O.OracleScene(rows).render(w, h, O.Constants(0.0, 1, a, 1), O.Settings(debug, bounces, 1.0, 1.0, 0), spp)
+    img.setflags(write=False)
+    return img
+
+
+@pytest.mark.parametrize("name,w,h,spp,bounces", [("c2", 24, 16, 2, 4), ("c3", 24, 16, 2, 8)])
+def test_skyref_without_a_sky_equals_oracle(name, w, h, spp, bounces):
+    """skyref's render loop with sky=None is pto_render, bit for bit."""
+    got = skyref.render(scenes.SCENES[name]().rows(), w, h, 1, 1, _aspect(w, h), bounces, spp)
+    ref = _oracle(name, w, h, spp, bounces)
+    assert ref[..., :3].mean() > 0
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+
+
+@pytest.mark.parametrize("with_sky", [False, True])
+@pytest.mark.parametrize("debug", [1, 2, 3])
+def test_skyref_debug_views_equal_oracle(debug, with_sky):
+    """The debug views, with a sky too: 1 and 2 never path trace, 3 shows the segment count."""
+    w, h = 12, 8
+    got = skyref.render(scenes.SCENES["c3"]().rows(), w, h, 1, 1, _aspect(w, h), 8, 1, debug=debug,
+                        sky=_test_sky() if with_sky else None)
+    assert np.array_equal(got.view(np.uint32), _oracle("c3", w, h, 1, 8, debug).view(np.uint32))
+
+
+@pytest.mark.parametrize("sun_ahead", [False, True])
+def test_empty_scene_shows_the_sky_itself(sun_ahead):
+    """No shape: every primary ray misses with throughput 1, so a texel is its
+    own ray's sky radiance, mixed into the cleared image -- computed here from
+    the formula of DESIGN.md 3.25 in numpy float32, not through skyref.  The
+    test sky's sun stands behind the default camera; a second sky puts one in
+    view."""
+    w, h = 16, 8
+    a = F(_aspect(w, h))
+    sky = _sky_light((0.9, 0.8, 0.7), (0.25, 0.45, 0.9), (0.2, 0.3, 1.0), (8.0, 7.0, 5.0), 15.0) if sun_ahead \
+        else _test_sky()
+    counts = {}
+    img = skyref.render(scenes.SCENES["empty"]().rows(), w, h, 1, 1, float(a), 4, 1, sky=sky, counts=counts)
+    assert counts["miss"] == w * h
+    bottom, top, sun_dir, sun_color = (np.array(list(v), np.float32) for v in (sky.bottom, sky.top, sky.sun_dir,
+                                                                               sky.sun_color))
+    in_sun = 0
+    with np.errstate(all="ignore"):
+        for y in range(h):
+            for x in range(w):
+                rng = P.Rng(P.gen_rng(x, y, 1, w, h))
+                jx = rng.f01() - F(0.5)
+                jy = rng.f01() - F(0.5)
+                ux = (((F(x) + jx) / F(w)) * F(2.0) - F(1.0)) * a
+                uy = ((F(y) + jy) / F(h)) * F(2.0) - F(1.0)
+                v = np.array([ux, uy, F(1.0)], np.float32)
+                rd = v / F(np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]))
+                t = rd[1] * F(0.5) + F(0.5)
+                g = bottom + (top - bottom) * t
+                if (rd[0] * sun_dir[0] + rd[1] * sun_dir[1]) + rd[2] * sun_dir[2] >= F(sky.sun_cos):
+                    g = g + sun_color
+                    in_sun += 1
+                wgt = F(1.0) / F(2)  # last_clear 1, first frame
+                want = np.zeros(3, np.float32) * (F(1.0) - wgt) + g * wgt
+                assert want.dtype == np.float32
+                assert np.array_equal(img[y, x, :3].view(np.uint32), want.view(np.uint32)), (x, y)
+                assert img[y, x, 3] == 1.0
+    assert in_sun == counts["sun"] and (0 < in_sun < w * h if sun_ahead else in_sun == 0)
+    # the gradient shows: the top row is bluer than the bottom row, the bottom row redder
+    assert img[h - 1, :, 2].mean() > img[0, :, 2].mean() and img[0, :, 0].mean() > img[h - 1, :, 0].mean()
+
+
+# samples whose path ended in a miss / of those, inside the sun's disc, as recorded when skyref was written
+# (a wrong gradient moves no count, but a wrong sun test, a wrong segment direction or a lost miss does)
+COUNTS = [
+    ("c2", 24, 16, 2, 4, "default", 637, 39),
+    ("c2", 24, 16, 2, 4, "pinhole", 624, 46),
+    ("c2", 24, 16, 2, 4, "lens", 649, 57),
+    ("c3", 24, 16, 2, 8, "default", 103, 15),
+    ("c3", 24, 16, 2, 8, "pinhole", 149, 12),
+    ("c3", 24, 16, 2, 8, "lens", 184, 14),
+    ("c2", 20, 13, 2, 4, "default", 432, 33),
+    ("c2", 20, 13, 2, 4, "pinhole", 431, 31),
+    ("c2", 20, 13, 2, 4, "lens", 430, 36),
+]
+
+
+@pytest.mark.parametrize("name,w,h,spp,bounces,kind,miss,sun", COUNTS)
+def test_sky_cases_reach_the_sky_and_the_sun(name, w, h, spp, bounces, kind, miss, sun):
+    """The GPU tests' cases: how many samples end in the sky and in the sun's
+    disc, and how much of the image the sky changes."""
+    rows = scenes.SCENES[name]().rows()
+    a = _aspect(w, h)
+    cam = _camera(kind)
+    counts = {}
+    img = skyref.render(rows, w, h, 1, 1, a, bounces, spp, camera=cam, sky=_test_sky(), counts=counts)
+    assert np.isfinite(img).all()
+    assert (counts["miss"], counts["sun"]) == (miss, sun)
+    assert sun >= 8
+    if name == "c3":
+        assert miss >= 100  # mostly later segments (c2's are mostly first segments)
+    dark = {}
+    off = skyref.render(rows, w, h, 1, 1, a, bounces, spp, camera=cam, counts=dark)
+    assert dark["miss"] == miss and dark["sun"] == 0  # the sky draws no random number: the paths are the same
+    changed = float(np.mean(np.any(img.view(np.uint32) != off.view(np.uint32), axis=-1)))
+    assert changed > (0.9 if name == "c2" else 0.2), changed
+
+
+def test_sky_light_defaults_and_rounding():
+    sky = _sky_light((0.5, 0.25, 0.125))
+    assert list(sky.top) == list(sky.bottom) == [0.5, 0.25, 0.125]  # top defaults to bottom: uniform ambient light
+    assert list(sky.sun_color) == [0.0, 0.0, 0.0]
+    assert sky.sun_cos == 1.0  # sun_angle 0
+    sky = _test_sky()
+    assert list(sky.bottom) == [float(F(v)) for v in (0.9, 0.8, 0.7)]
+    assert list(sky.top) == [float(F(v)) for v in (0.25, 0.45, 0.9)]
+    assert list(sky.sun_color) == [8.0, 7.0, 5.0]
+    d = np.array(list(sky.sun_dir), np.float64)
+    assert abs(np.dot(d, d) - 1.0) < 1e-6
+    assert np.allclose(d, np.array([0.4, 0.7, -0.6]) / np.linalg.norm([0.4, 0.7, -0.6]), atol=1e-6)
+    assert sky.sun_cos == float(F(np.cos(np.radians(30.0))))
+    assert abs(sky.sun_cos - 0.8660254) < 1e-6
+
+
+@pytest.mark.parametrize("kw", [
+    dict(bottom=(0.1, 0.1, 0.1), sun_direction=(0.0, 0.0, 0.0)),  # zero direction
+    dict(bottom=(0.1, -0.1, 0.1)),                                # negative colour
+    dict(bottom=(0.1, 0.1, 0.1), top=(0.0, 0.0, -1.0)),
+    dict(bottom=(0.1, 0.1, 0.1), sun_color=(-1.0, 0.0, 0.0)),
+    dict(bottom=(0.1, 0.1)),                                      # wrong shape
+    dict(bottom=(0.1, 0.1, 0.1), top=(1.0, 1.0, 1.0, 1.0)),
+    dict(bottom=(0.1, 0.1, 0.1), sun_direction=(1.0, 0.0)),
+    dict(bottom=(0.1, 0.1, 0.1), sun_color=0.5),
+])
+def test_sky_light_rejects(kw):
+    with pytest.raises(ValueError):
+        _sky_light(**kw)
