@@ -28,6 +28,7 @@ PT_COMBINE_ASSIGN, PT_COMBINE_UNION, PT_COMBINE_SUBTRACTION = 0, 1, 2
 PT_SO_SCALAR, PT_SO_VEC3, PT_SO_ONE, PT_SO_TORUS = 0, 1, 2, 3
 PT_COMM_ID_BYTES = 128
 PT_DISPLAY_RGBA32F, PT_DISPLAY_SRGB8 = 0, 1
+PT_DENOISE_LINEAR = 2  # pt_denoise only: linear RGBA32F in accumulation order
 PT_STAT_COUNT = 32
 STAT_NAMES = (
     "samples", "segments", "march_steps", "normal_maps", "shaded", "aabb_tests", "xform_union", "xform_shape",
@@ -49,7 +50,7 @@ SYMBOLS = (
     "pt_destroy", "pt_abi_version", "pt_device_math", "pt_check_sqrt_exhaustive", "pt_check_div_exhaustive",
     "pt_check_div_random", "pt_check_box_random", "pt_check_div_k", "pt_display", "pt_write_accum",
     "pt_compile_scene_keyed", "pt_save_rgba8", "pt_comm_size", "pt_traffic_probe", "pt_scene_kernel_source",
-    "pt_set_camera", "pt_get_camera", "pt_set_sky", "pt_get_sky",
+    "pt_set_camera", "pt_get_camera", "pt_set_sky", "pt_get_sky", "pt_render_guides", "pt_read_guides", "pt_denoise",
 )
 PT_MATH = {"max": 0, "min": 1, "sqrt": 2, "sqrtf": 3, "sin": 4, "cos": 5, "div": 6, "fma": 7}
 
@@ -80,6 +81,13 @@ class Sky(Structure):
 
     _fields_ = [("bottom", c_float * 3), ("top", c_float * 3), ("sun_dir", c_float * 3), ("sun_color", c_float * 3),
                 ("sun_cos", c_float)]
+
+
+class DenoiseParams(Structure):
+    """pt_denoise_params: the a-trous filter of ``pt_denoise`` (new)."""
+
+    _fields_ = [("iterations", c_uint32), ("normal_power_log2", c_uint32), ("sigma_color", c_float),
+                ("sigma_depth", c_float), ("sigma_albedo", c_float)]
 
 
 class SceneNode(Structure):
@@ -116,7 +124,7 @@ class Aabb(Structure):
 
 
 assert ctypes.sizeof(Constants) == 16 and ctypes.sizeof(Settings) == 20
-assert ctypes.sizeof(Camera) == 56 and ctypes.sizeof(Sky) == 52
+assert ctypes.sizeof(Camera) == 56 and ctypes.sizeof(Sky) == 52 and ctypes.sizeof(DenoiseParams) == 20
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
 
@@ -187,6 +195,9 @@ def lib() -> ctypes.CDLL:
         "pt_traffic_probe": (c_int, [c_int, c_uint32, POINTER(c_float), POINTER(c_uint64)]),
         "pt_display": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
         "pt_write_accum": (c_int, [c_void_p, POINTER(c_float), c_size_t]),
+        "pt_render_guides": (c_int, [ctx, POINTER(Constants), POINTER(Settings)]),
+        "pt_read_guides": (c_int, [ctx, POINTER(c_float), POINTER(c_float), c_size_t]),
+        "pt_denoise": (c_int, [ctx, POINTER(DenoiseParams), c_int, c_void_p, c_size_t]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("PT_LIB") and not hasattr(L, name):

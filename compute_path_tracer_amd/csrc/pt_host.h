@@ -19,6 +19,23 @@ int pt_bin_trace_blocks_per_cu(bool stats);  // occupancy of the interpreter tra
 // trace pass wrote hit quads (taps in the shade pass), not hit records
 void pt_launch_bin_sky(const PtPass &P, bool quads, unsigned grid, hipStream_t stream);
 void pt_launch_display(const float *img, uint32_t w, uint32_t h, int fmt, void *out, hipStream_t stream);
+// the denoiser's guide images (pt_render_guides): L as a dispatch takes it, over every tile, a lens as its pinhole
+void pt_launch_guides(const PtLaunch &L, float *g0, float *g1, hipStream_t stream);
+// one iteration of the a-trous filter (pt_denoise): every iteration's constants travel in the launch arguments
+#define PT_ATROUS_BX 64            // direct form: block 64 x 4, a wave = one row segment
+#define PT_ATROUS_BY 4
+#define PT_ATROUS_T 16             // LDS form: 16 x 16 tile + halo
+#define PT_ATROUS_LDS_MAX_STEP 2   // ... for steps 1 and 2
+struct PtAtrous {
+    const float4 *in, *g0, *g1;
+    float4 *out;
+    int32_t w, h;
+    int32_t iter;   // taps at step 1 << iter
+    int32_t npow;   // normal_power_log2
+    float ka;
+    float kc[PT_DENOISE_MAX_ITERATIONS], kz[PT_DENOISE_MAX_ITERATIONS];
+};
+void pt_launch_atrous(const PtAtrous &A, bool lds, hipStream_t stream);
 
 // Expand (program, data[]) into the device tables (see pt_device.h).
 int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, const float *data, uint32_t n,

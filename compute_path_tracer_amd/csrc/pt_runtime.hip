@@ -45,6 +45,7 @@ struct JitBuild {
 
 static_assert(sizeof(pt_camera) == 14 * 4, "pt_camera layout");
 static_assert(sizeof(pt_sky) == 13 * 4, "pt_sky layout");
+static_assert(sizeof(pt_denoise_params) == 5 * 4, "pt_denoise_params layout");
 // the reference's fixed view as a pt_camera (what pt_get_camera reports for it)
 static const pt_camera kDefaultCamera = {{0.0f, 0.0f, -3.0f}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f},
                                          {0.0f, 0.0f, 1.0f}, 0.0f, 1.0f};
@@ -146,6 +147,16 @@ struct pt_ctx {
     size_t cap_display = 0;
     hipEvent_t dev0 = nullptr, dev1 = nullptr;
     bool display_timed = false;
+    // denoiser (pt_render_guides / pt_denoise): the guide planes g0 = {n, t} and
+    // g1 = {albedo, hit} (16 B/px each), the filter's two ping-pong images
+    // (16 B/px each), grown on first use; events around their kernels
+    float *d_guides[2] = {nullptr, nullptr};
+    float *d_filter[2] = {nullptr, nullptr};
+    size_t cap_guides[2] = {0, 0}, cap_filter[2] = {0, 0};
+    bool guides_valid = false;
+    int denoise_lds = 1;  // pt_set_option "denoise_lds": LDS-staged taps at steps 1 and 2 (-19 % on five iterations: EXPERIMENTS.md)
+    hipEvent_t gev0 = nullptr, gev1 = nullptr, nev0 = nullptr, nev1 = nullptr;
+    bool guide_timed = false, denoise_timed = false;
     std::string jit_log;
     double jit_seconds = 0.0;
     std::string err;
@@ -548,8 +559,7 @@ int pt_create(int hip_device, uint32_t width, uint32_t height, pt_ctx **out) {
     return PT_OK;
 }
 
-int pt_resize_clear(pt_ctx *c, uint32_t width, uint32_t height) {
-    if (!c) return PT_ERR_INVALID;
+static int resize_clear(pt_ctx *c, uint32_t width, uint32_t height) {
     HIPCHK(c, hipSetDevice(c->device));
     if (width == c->width && height == c->height) {
         HIPCHK(c, hipMemsetAsync(c->accum, 0, std::max<size_t>(size_t(width) * height * 16, 16), c->stream));
@@ -557,6 +567,12 @@ int pt_resize_clear(pt_ctx *c, uint32_t width, uint32_t height) {
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return alloc_image(c, width, height);
+}
+
+int pt_resize_clear(pt_ctx *c, uint32_t width, uint32_t height) {
+    if (!c) return PT_ERR_INVALID;
+    c->guides_valid = false;
+    return resize_clear(c, width, height);
 }
 
 int pt_set_program(pt_ctx *c, const pt_op *ops, uint32_t n_ops, const pt_aabb *aabbs, uint32_t n_aabb,
@@ -588,6 +604,7 @@ int pt_set_program(pt_ctx *c, const pt_op *ops, uint32_t n_ops, const pt_aabb *a
     for (uint32_t i = 0; i < n_aabb; ++i)
         if (aabbs[i].back < 0 || aabbs[i].back >= int32_t(n_check) || aabbs[i].so_kind > PT_SO_TORUS)
             return fail(c, PT_ERR_INVALID, "bad aabb record");
+    c->guides_valid = false;
     c->ops.assign(ops, ops + n_ops);
     c->aabbs.assign(aabbs, aabbs + n_aabb);
     c->n_check = n_check;
@@ -606,6 +623,7 @@ int pt_set_data(pt_ctx *c, const float *data, uint32_t n) {
     std::string err;
     int rc = pt_derive(c->ops, c->aabbs, data, n, nodes, boxes, mats, err);
     if (rc != PT_OK) return fail(c, rc, err);
+    c->guides_valid = false;
     HIPCHK(c, hipSetDevice(c->device));
     // stream-ordered upload: in-flight dispatches finish with the old tables
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -636,7 +654,7 @@ int pt_set_tiles(pt_ctx *c, uint32_t rank, uint32_t nranks) {
     if (nranks == 0 || rank >= nranks) return fail(c, PT_ERR_INVALID, "rank must be < nranks");
     c->rank = rank;
     c->nranks = nranks;
-    return pt_resize_clear(c, c->width, c->height);
+    return resize_clear(c, c->width, c->height);  // (the size stays: the guide images, of every pixel, stay valid)
 }
 
 int pt_set_camera(pt_ctx *c, const pt_camera *cam) {
@@ -644,6 +662,7 @@ int pt_set_camera(pt_ctx *c, const pt_camera *cam) {
     if (!cam) {
         c->cam_mode = PT_CAM_DEFAULT;
         c->cam = kDefaultCamera;
+        c->guides_valid = false;
         return PT_OK;
     }
     float v[14];
@@ -655,6 +674,7 @@ int pt_set_camera(pt_ctx *c, const pt_camera *cam) {
         return fail(c, PT_ERR_INVALID, "camera focus must be > 0 with an aperture");
     c->cam = *cam;
     c->cam_mode = cam->aperture > 0.0f ? PT_CAM_LENS : PT_CAM_PINHOLE;
+    c->guides_valid = false;
     return PT_OK;
 }
 
@@ -1266,6 +1286,119 @@ int pt_display(pt_ctx *c, int format, void *out, size_t bytes) {
     return PT_OK;
 }
 
+// ---- denoiser -------------------------------------------------
+int pt_render_guides(pt_ctx *c, const pt_constants *k, const pt_settings *s) {
+    PtLaunch L;
+    int rc = make_launch(c, k, s, 1, L);
+    if (rc != PT_OK) return rc;
+    // every tile, whatever pt_set_tiles says; a lens as its pinhole (no lens draw, no rng at all)
+    L.n_tiles = int32_t(int64_t(L.tiles_x) * int64_t((c->height + PT_TILE - 1) / PT_TILE));
+    L.rank = 0;
+    L.nranks = 1;
+    if (L.cam_mode == PT_CAM_LENS) L.cam_mode = PT_CAM_PINHOLE;
+    L.sky_mode = PT_SKY_OFF;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t plane = std::max<size_t>(size_t(c->width) * c->height * 16, 16);
+    for (int i = 0; i < 2; ++i)
+        if ((rc = ensure(c, reinterpret_cast<void **>(&c->d_guides[i]), c->cap_guides[i], plane)) != PT_OK) return rc;
+    if (!c->gev0) {
+        HIPCHK(c, hipEventCreate(&c->gev0));
+        HIPCHK(c, hipEventCreate(&c->gev1));
+    }
+    HIPCHK(c, hipEventRecord(c->gev0, c->stream));
+    pt_launch_guides(L, c->d_guides[0], c->d_guides[1], c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->gev1, c->stream));
+    c->guide_timed = true;
+    c->guides_valid = true;
+    return PT_OK;
+}
+
+int pt_read_guides(pt_ctx *c, float *g0, float *g1, size_t bytes_each) {
+    if (!c) return PT_ERR_INVALID;
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "guides stale: call pt_render_guides");
+    const size_t need = size_t(c->width) * c->height * 16;
+    if (bytes_each < need) return fail(c, PT_ERR_SIZE, "guide buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (g0 && need) HIPCHK(c, hipMemcpyAsync(g0, c->d_guides[0], need, hipMemcpyDeviceToHost, c->stream));
+    if (g1 && need) HIPCHK(c, hipMemcpyAsync(g1, c->d_guides[1], need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_denoise(pt_ctx *c, const pt_denoise_params *p, int format, void *out, size_t bytes) {
+    if (!c) return PT_ERR_INVALID;
+    if (!p) return fail(c, PT_ERR_INVALID, "null denoise parameters");
+    if (format != PT_DISPLAY_RGBA32F && format != PT_DISPLAY_SRGB8 && format != PT_DENOISE_LINEAR)
+        return fail(c, PT_ERR_INVALID, "bad denoise format");
+    if (p->iterations < 1 || p->iterations > PT_DENOISE_MAX_ITERATIONS)
+        return fail(c, PT_ERR_INVALID, "denoise iterations must be in [1, 8]");
+    if (p->normal_power_log2 > 8) return fail(c, PT_ERR_INVALID, "denoise normal_power_log2 must be in [0, 8]");
+    for (float v : {p->sigma_color, p->sigma_depth, p->sigma_albedo})
+        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "denoise sigma must be finite and >= 0");
+    // the iterations' constants, in f32: the scaled sigma, its square, one
+    // division of 1 (a term that is off: 0)
+    PtAtrous A;
+    std::memset(&A, 0, sizeof A);
+    auto inv_sq = [](float sigma, float scale) {
+        if (sigma == 0.0f) return 0.0f;
+        const float v = sigma * scale;
+        const float sq = v * v;
+        return 1.0f / sq;
+    };
+    A.ka = inv_sq(p->sigma_albedo, 1.0f);
+    bool finite = std::isfinite(A.ka);
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        A.kc[i] = inv_sq(p->sigma_color, std::ldexp(1.0f, -int(i)));
+        A.kz[i] = inv_sq(p->sigma_depth, std::ldexp(1.0f, int(i)));
+        finite = finite && std::isfinite(A.kc[i]) && std::isfinite(A.kz[i]);
+    }
+    if (!finite) return fail(c, PT_ERR_INVALID, "denoise sigma too small: 1 / sigma^2 is not finite");
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "guides stale: call pt_render_guides");
+    const size_t texels = size_t(c->width) * c->height;
+    const size_t need = texels * (format == PT_DISPLAY_SRGB8 ? 4 : 16);
+    if (!out || bytes < need) return fail(c, PT_ERR_SIZE, "denoise output buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    for (int i = 0; i < 2; ++i)
+        if ((rc = ensure(c, reinterpret_cast<void **>(&c->d_filter[i]), c->cap_filter[i], std::max<size_t>(texels * 16, 16))) !=
+            PT_OK)
+            return rc;
+    if (format != PT_DENOISE_LINEAR && (rc = ensure(c, &c->d_display, c->cap_display, std::max<size_t>(need, 16))) != PT_OK)
+        return rc;
+    if (!c->nev0) {
+        HIPCHK(c, hipEventCreate(&c->nev0));
+        HIPCHK(c, hipEventCreate(&c->nev1));
+    }
+    A.g0 = reinterpret_cast<const float4 *>(c->d_guides[0]);
+    A.g1 = reinterpret_cast<const float4 *>(c->d_guides[1]);
+    A.w = int32_t(c->width);
+    A.h = int32_t(c->height);
+    A.npow = int32_t(p->normal_power_log2);
+    // accumulation image -> filter[0] -> filter[1] -> filter[0] ...: the image itself is only read
+    const float *src = c->accum;
+    HIPCHK(c, hipEventRecord(c->nev0, c->stream));
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        A.in = reinterpret_cast<const float4 *>(src);
+        A.out = reinterpret_cast<float4 *>(c->d_filter[i & 1]);
+        A.iter = int32_t(i);
+        pt_launch_atrous(A, c->denoise_lds != 0, c->stream);
+        HIPCHK(c, hipGetLastError());
+        src = c->d_filter[i & 1];
+    }
+    HIPCHK(c, hipEventRecord(c->nev1, c->stream));
+    c->denoise_timed = true;
+    const void *result = src;
+    if (format != PT_DENOISE_LINEAR) {
+        pt_launch_display(src, c->width, c->height, format, c->d_display, c->stream);
+        HIPCHK(c, hipGetLastError());
+        result = c->d_display;
+    }
+    if (need) HIPCHK(c, hipMemcpyAsync(out, result, need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
 int pt_accum_device_ptr(pt_ctx *c, void **dev_ptr, size_t *bytes) {
     if (!c || !dev_ptr || !bytes) return PT_ERR_INVALID;
     *dev_ptr = c->accum;
@@ -1400,6 +1533,11 @@ int pt_set_option(pt_ctx *c, const char *key, int value) {
         c->shade_taps = value;
         return PT_OK;
     }
+    if (!std::strcmp(key, "denoise_lds")) {
+        if (value < 0 || value > 1) return fail(c, PT_ERR_INVALID, "denoise_lds must be 0 or 1");
+        c->denoise_lds = value;
+        return PT_OK;
+    }
     if (!std::strcmp(key, "shade_batch")) {
         if (value < 1 || value > 64) return fail(c, PT_ERR_INVALID, "shade_batch must be in [1, 64]");
         c->shade_batch = value;
@@ -1454,6 +1592,17 @@ int pt_get_option(pt_ctx *c, const char *key, double *value) {
         if (c->display_timed) HIPCHK(c, hipEventElapsedTime(&ms, c->dev0, c->dev1));
         *value = ms;
     }
+    else if (!std::strcmp(key, "guide_ms") || !std::strcmp(key, "denoise_ms")) {
+        const bool g = key[0] == 'g';
+        float ms = 0.0f;
+        if (g ? c->guide_timed : c->denoise_timed) {
+            HIPCHK(c, hipEventSynchronize(g ? c->gev1 : c->nev1));  // (pt_render_guides is asynchronous)
+            HIPCHK(c, hipEventElapsedTime(&ms, g ? c->gev0 : c->nev0, g ? c->gev1 : c->nev1));
+        }
+        *value = ms;
+    }
+    else if (!std::strcmp(key, "guides_valid")) *value = c->guides_valid ? 1.0 : 0.0;
+    else if (!std::strcmp(key, "denoise_lds")) *value = double(c->denoise_lds);
     else if (!std::strcmp(key, "trace_ms")) HIPCHK(c, event_log_ms(c->tlog, value));  // summed over the trace passes
     else if (!std::strcmp(key, "shade_ms")) HIPCHK(c, event_log_ms(c->slog, value));  // summed over the shade passes
     else if (!std::strcmp(key, "sky_ms")) HIPCHK(c, event_log_ms(c->klog, value));  // summed over the sky passes (pt_set_sky)
@@ -1509,6 +1658,12 @@ void pt_destroy(pt_ctx *c) {
     (void)hipFree(c->d_display);
     if (c->dev0) (void)hipEventDestroy(c->dev0);
     if (c->dev1) (void)hipEventDestroy(c->dev1);
+    for (int i = 0; i < 2; ++i) {
+        (void)hipFree(c->d_guides[i]);
+        (void)hipFree(c->d_filter[i]);
+    }
+    for (hipEvent_t e : {c->gev0, c->gev1, c->nev0, c->nev1})
+        if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

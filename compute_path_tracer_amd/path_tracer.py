@@ -327,6 +327,52 @@ class PathTracer:
         self._chk("pt_display", self._L.pt_display(self._ctx, fmt, out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
         return out
 
+    # -- denoiser (new: guide images + an edge-stopping a-trous wavelet) ------
+    def render_guides(self, constants: Optional[N.Constants] = None) -> None:
+        """pt_render_guides: the first-hit normal / depth / albedo images of
+        the view in force (one jitter-free primary ray per pixel, a lens as
+        its pinhole).  Aspect as ``render`` / ``update`` form it from the
+        window, fov from the settings; or explicit ``constants``.  Needed
+        again after a resize or clear, a scene change or a camera move."""
+        c = constants
+        if c is None:
+            c = N.Constants(time=self.constants.time, frame=self.constants.frame,
+                            aspect=float(np.float32(self.window[0]) / np.float32(self.window[1])),
+                            last_clear=self.constants.last_clear)
+        self._chk("pt_render_guides", self._L.pt_render_guides(self._ctx, ctypes.byref(c), ctypes.byref(self.settings)))
+
+    def read_guides(self):
+        """(g0, g1), float32 [height][width][4] each, rows as read_image:
+        g0 = (normal.xyz, t), g1 = (albedo.rgb, 1 hit / 0 miss)."""
+        w, h = self.size
+        g0, g1 = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        self._chk("pt_read_guides", self._L.pt_read_guides(self._ctx, g0.ctypes.data_as(fp), g1.ctypes.data_as(fp),
+                                                            g0.nbytes))
+        return g0, g1
+
+    DENOISE_OUTPUTS = {"linear": N.PT_DENOISE_LINEAR, "display": N.PT_DISPLAY_RGBA32F, "srgb8": N.PT_DISPLAY_SRGB8}
+
+    def denoise(self, iterations: int = 5, sigma_color: float = 2.0, sigma_depth: float = 0.05,
+                sigma_albedo: float = 0.1, normal_power_log2: int = 5, output: str = "linear") -> np.ndarray:
+        """pt_denoise: the accumulation image through ``iterations`` passes of
+        the edge-stopping a-trous wavelet (step 1, 2, 4, ...), steered by the
+        guide images of ``render_guides``; the image itself is left as it is.
+        ``output``: "linear" (float32 [h][w][4], rows as read_image),
+        "display" / "srgb8" (the result through the display pass, as
+        ``display(srgb8=False / True)`` returns it).  A sigma of 0 switches
+        its term off."""
+        if output not in self.DENOISE_OUTPUTS:
+            raise ValueError(f"output must be one of {sorted(self.DENOISE_OUTPUTS)}, got {output!r}")
+        p = N.DenoiseParams(iterations=int(iterations), normal_power_log2=int(normal_power_log2),
+                            sigma_color=float(sigma_color), sigma_depth=float(sigma_depth),
+                            sigma_albedo=float(sigma_albedo))
+        w, h = self.size
+        out = np.empty((h, w, 4), dtype=np.uint8 if output == "srgb8" else np.float32)
+        self._chk("pt_denoise", self._L.pt_denoise(self._ctx, ctypes.byref(p), self.DENOISE_OUTPUTS[output],
+                                                    out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+        return out
+
     # -- RCCL ------------------------------------------------------------
     @staticmethod
     def comm_unique_id() -> bytes:

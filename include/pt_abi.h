@@ -277,6 +277,50 @@ int pt_dispatch_stats(pt_ctx *ctx, const pt_constants *c, const pt_settings *s, 
 #define PT_DISPLAY_RGBA32F 0
 #define PT_DISPLAY_SRGB8 1
 int pt_display(pt_ctx *ctx, int format, void *out, size_t bytes);
+/* Denoiser (new; DESIGN.md 3.26 has the f32 steps of both stages).
+ * Guide images: one primary ray per pixel through the jitter-free screen point
+ * the reference's calc_uv forms for it, from the camera in force (a
+ * lens as its pinhole), no random numbers, every pixel whatever pt_set_tiles
+ * says.  Two RGBA32F planes of w*h texels in the accumulation image's order:
+ *   g0 = {normal.xyz, t}            (normal 0 where the ray misses)
+ *   g1 = {albedo.rgb, 1 hit / 0 miss}
+ * Uses c->aspect and s->fov.  Asynchronous, on the context's stream; sets the
+ * context's "guides valid" flag, which pt_resize_clear, pt_set_program,
+ * pt_set_data and pt_set_camera clear (pt_set_sky, pt_set_tiles, dispatches
+ * and option changes do not).  PT_ERR_STATE without program or data. */
+int pt_render_guides(pt_ctx *ctx, const pt_constants *c, const pt_settings *s);
+/* Blocking copy of the guide planes (w*h*16 bytes each); either pointer may be
+ * NULL.  PT_ERR_STATE while the guides are not valid. */
+int pt_read_guides(pt_ctx *ctx, float *g0, float *g1, size_t bytes_each);
+/* Edge-stopping a-trous wavelet filter (Dammertz et al. 2010) of the
+ * accumulation image, steered by the guide images.  Iteration i (from 0)
+ * taps a 5x5 B3 kernel at step 1 << i; a tap's weight is divided by
+ * (1 + |dcolour|^2 kc_i) (1 + |dalbedo|^2 ka) (1 + dt^2 kz_i) and multiplied
+ * by max(dot(n_p, n_q), 0)^(2^normal_power_log2), with
+ *   kc_i = 1 / (sigma_color * 2^-i)^2, kz_i = 1 / (sigma_depth * 2^i)^2,
+ *   ka = 1 / sigma_albedo^2            (a sigma of 0 switches its term off);
+ * hit and miss texels never mix, and a non-finite texel stays as it is and
+ * spreads nowhere. */
+typedef struct {                 /* 20 bytes */
+    uint32_t iterations;         /* 1..8 */
+    uint32_t normal_power_log2;  /* 0..8: the clamped normal dot product is squared this many times */
+    float sigma_color;           /* halved every iteration; 0 = term off */
+    float sigma_depth;           /* doubled every iteration; 0 = term off */
+    float sigma_albedo;          /* 0 = term off */
+} pt_denoise_params;
+/* Reads the accumulation image and never writes it (a progressive render goes
+ * on afterwards as if it had not been called); filters through two device
+ * buffers and copies the result out, blocking:
+ *   PT_DENOISE_LINEAR: linear RGBA32F in accumulation order, w*h*16 bytes;
+ *   PT_DISPLAY_RGBA32F / PT_DISPLAY_SRGB8: through the display pass, with
+ *     pt_display's byte sizes and row orders.
+ * PT_ERR_STATE while the guides are not valid; PT_ERR_INVALID for a NULL p, a
+ * bad format, iterations or normal_power_log2 out of range, a negative or
+ * non-finite sigma, or one whose kc_i / kz_i / ka is not finite; PT_ERR_SIZE
+ * as pt_display. */
+#define PT_DENOISE_LINEAR 2
+#define PT_DENOISE_MAX_ITERATIONS 8
+int pt_denoise(pt_ctx *ctx, const pt_denoise_params *p, int format, void *out, size_t bytes);
 /* Tuning knobs: "kernel" (0 auto = 3, 1 simple one-path-per-lane, 2 tile-
  * resident wavefront state machine, 3 mask-binned passes: per bounce, the
  * rays of a chunk of frames are grouped by their bounds() check set before
@@ -299,7 +343,9 @@ int pt_display(pt_ctx *ctx, int format, void *out, size_t bytes);
  * every value edit; 2, the default: tier-up -- the table kernel runs at
  * once, and a values-baked build compiled on a worker thread replaces it
  * while the values stay unchanged) and "jit_wait" (block until a pending
- * tier-up build is installed).  Results are bit-identical for every value. */
+ * tier-up build is installed) and "denoise_lds" (pt_denoise: 1, the default,
+ * stages a block's tile and halo in LDS for the iterations of step 1 and 2;
+ * 0 loads every tap directly).  Results are bit-identical for every value. */
 int pt_set_option(pt_ctx *ctx, const char *key, int value);
 /* Read back: "jit_active" (1 when the scene-specialised kernel is loaded),
  * "jit_seconds" (last hipRTC compile time), "jit_tier_active" /
@@ -311,7 +357,9 @@ int pt_set_option(pt_ctx *ctx, const char *key, int value);
  * dispatch's binned trace passes, HIP events on each pipeline's stream),
  * "shade_ms" / "shade_launches" (the same for its shade passes), "sky_ms" /
  * "sky_launches" (the same for its sky passes, pt_set_sky; 0 without a sky), "display_ms"
- * (device time of the last pt_display's kernel), "gen_trace" / "gen_norec"
+ * (device time of the last pt_display's kernel), "guide_ms" / "denoise_ms"
+ * (device time of the last pt_render_guides' kernel / of all iterations of the
+ * last pt_denoise, without its display pass), "guides_valid", "gen_trace" / "gen_norec"
  * (the last timed binned dispatch's first pass made its own camera rays /
  * and stored no ray records for shade pass 0). */
 int pt_get_option(pt_ctx *ctx, const char *key, double *value);
