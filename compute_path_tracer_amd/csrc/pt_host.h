@@ -1,8 +1,10 @@
-// pt_host.h -- host-side internals shared by pt_runtime.hip and pt_jit.cpp.
+// pt_host.h -- host-side internals shared by the runtime's host files (pt_runtime.hip, pt_bin_host.cpp,
+// pt_options.cpp, pt_derive.cpp) and pt_jit.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <future>
 #include <string>
 #include <vector>
 
@@ -44,25 +46,38 @@ int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, 
 // Margin constant of the map() bound; NaN: no bound.
 float pt_bound_k(const std::vector<PtNode> &nodes);
 
-// Scene-specialised kernels (hipRTC).
-struct PtJitModule {
-    hipModule_t module = nullptr;
-    hipFunction_t render = nullptr;
-    hipFunction_t render_stats = nullptr;
-    hipFunction_t trace = nullptr;        // binned pipeline trace pass (pt_binned.h)
-    hipFunction_t trace_stats = nullptr;
-    hipFunction_t trace_m = nullptr;        // march-only trace pass (normal taps in the shade pass)
-    hipFunction_t trace_m_stats = nullptr;
-    hipFunction_t shade_t = nullptr;        // shade pass with the normal taps (JitMapB)
-    hipFunction_t shade_t_stats = nullptr;
-    hipFunction_t gen = nullptr;  // camera rays + the scene's straight-line bounds()
-    hipFunction_t gen_stats = nullptr;
-    hipFunction_t trace_g = nullptr;  // first pass with its own camera rays (PtPass gen_trace)
+// Scene-specialised kernels (hipRTC): a loaded code object and its kernels.
+enum PtJitFn {
+    kJitRender,       // pt_wave_jit: the tile-resident wave kernel
+    kJitRenderStats,
+    kJitTrace,        // binned pipeline trace pass (pt_binned.h)
+    kJitTraceStats,
+    kJitTraceM,       // march-only trace pass (normal taps in the shade pass)
+    kJitTraceMStats,
+    kJitShadeT,       // shade pass with the normal taps (JitMapB)
+    kJitShadeTStats,
+    kJitGen,          // camera rays + the scene's straight-line bounds()
+    kJitGenStats,
+    kJitTraceG,       // first pass with its own camera rays (PtPass gen_trace)
     // the kernels that make camera rays, built for a posed camera (pt_set_camera; pt_path.h PT_CAMK_POSED):
     // gen pass, first pass, shade pass 0 -- the ones above serve the fixed camera only
-    hipFunction_t gen_c = nullptr, trace_gc = nullptr, shade_tc = nullptr;
+    kJitGenC,
+    kJitTraceGC,
+    kJitShadeTC,
+    kJitFnCount
+};
+struct PtJitModule {
+    hipModule_t module = nullptr;
+    hipFunction_t fn[kJitFnCount] = {};
     std::string key;  // generated source
 };
+// The scene kernel of one stage of a dispatch.  stats: the instrumented run;
+// posed: a pt_set_camera view; taps_shade: normal taps in the shade pass;
+// gen_norec: the first pass stored no ray records.  nullptr: the stage has no
+// scene kernel in this configuration (the ahead-of-time one runs).
+enum class PtJitStage { Render, Gen, Trace, TraceFirst, Shade };
+hipFunction_t pt_jit_select(const PtJitModule &m, PtJitStage stage, bool stats, bool posed, bool taps_shade,
+                            bool gen_norec);
 
 // Source of the specialised kernel for these derived nodes.  bake=false:
 // only the topology, per-node flags and material indices enter (values stay
@@ -77,3 +92,43 @@ bool pt_jit_compile_source(const std::string &src, std::vector<char> &code, std:
 // Load a code object on the current device.
 bool pt_jit_load(const std::vector<char> &code, PtJitModule &m, std::string &err);
 void pt_jit_unload(PtJitModule &m);
+
+// A context's scene kernels and their lifecycle (pt_jit.cpp).  A code object
+// and where it came from: compiled by this process's hipRTC, or read from the
+// shipped on-disk cache (lib/jitcache)
+enum PtJitFrom { kJitCompiled = 0, kJitDisk = 1 };
+struct PtJitBuild {
+    std::vector<char> code;  // empty: the compile failed (log set)
+    double seconds = 0.0;
+    int from = kJitCompiled;
+};
+struct PtJitState {
+    int enabled = 1;  // pt_set_option "jit": 1 use per-scene hipRTC kernels, 0 interpreter
+    int bake = 2;     // "jit_bake": 0 values from the node table, 1 baked as literals, 2 tier-up
+    PtJitModule mod;  // scene kernel for the topology (key = its source)
+    // tier-up (bake 2): the same kernel with the current values baked in as
+    // literals, compiled on a worker thread and used once ready while the
+    // values stay unchanged -- value edits never wait for a compile
+    PtJitModule tier;
+    std::string tier_want;  // baked source for the current values
+    std::string tier_job_src;
+    std::string tier_failed;  // a baked source that did not build (not retried)
+    // code object (empty: compile failed) and its compile seconds; the worker
+    // returns both through the future, so no field is shared with it
+    std::future<PtJitBuild> tier_job;
+    double seconds = 0.0, tier_seconds = 0.0;
+    int from = -1, tier_from = -1;  // where the loaded builds came from (PtJitFrom)
+    std::string log;
+};
+// (Re)build the scene kernel when the generated source changed.  A failure
+// leaves the interpreter kernel in use and records the log.
+void pt_jit_refresh(PtJitState &j, const std::vector<PtNode> &nodes, const std::vector<PtAabb> &boxes,
+                    bool fast_bounds);
+// Install a finished tier-up compile if it is still the one the current
+// values want; start the wanted one if nothing is pending.  wait: block on a
+// pending compile first.
+void pt_jit_poll(PtJitState &j, bool wait);
+// The scene kernel in use: the tier-up build when loaded, else the topology one.
+const PtJitModule *pt_jit_active(const PtJitState &j);
+void pt_jit_disable(PtJitState &j);  // unload both builds and want no tier-up (until the next pt_jit_refresh)
+void pt_jit_destroy(PtJitState &j);  // wait for a pending compile, then unload

@@ -1,6 +1,6 @@
 """Distance-bound culling of the scene kernels, host side.
 
-The bound data (PtNode.pad[0], pt_runtime.hip pt_cull_bounds) is read back
+The bound data (PtNode.pad[0], pt_derive.cpp pt_cull_bounds) is read back
 from the values-baked hipRTC source (exact hex literals) and recomputed here
 from the same baked node values; the generated map() must carry the parent
 rule exactly for the unions the rule allows.  No GPU: hipRTC cross-compiles.

@@ -1,0 +1,191 @@
+"""GPU: the option surface of pt_set_option / pt_get_option (include/pt_abi.h):
+which keys exist in each direction, every settable key's range, the
+pt_last_error text of a refused value and that it leaves the previous value
+in place, what a fresh context reads, and what one small binned dispatch
+leaves behind.  An 8 x 8 context, scene c1, 4 bounces.
+"""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+
+from compute_path_tracer_amd import _native as N
+from compute_path_tracer_amd import scenes
+from compute_path_tracer_amd.path_tracer import PathTracer
+from compute_path_tracer_amd.sdf_editor import CompData
+
+pytestmark = pytest.mark.gpu
+
+W = H = 8
+BOUNCES = 4
+SPP = 4
+LANES = 2
+INT_MAX = 2**31 - 1
+
+# key: (lowest accepted, highest accepted, refused values, pt_last_error of a refusal, readable)
+SETTABLE = {
+    "kernel": (0, 3, (-1, 4), "bad kernel id", True),  # PT_KERNEL_AUTO .. PT_KERNEL_BINNED
+    "jit": (0, 1, (-1, 2), "jit must be 0 or 1", False),
+    "jit_bake": (0, 2, (-1, 3), "jit_bake must be 0, 1 or 2", False),
+    "bin_samples": (64, INT_MAX, (63,), "bin_samples must be >= 64", True),  # (no upper bound below int's)
+    "bin_lanes": (1, 4, (0, 5), "bin_lanes must be in [1, 4]", True),
+    "bin_table": (0, 1, (-1, 2), "bin_table must be 0 or 1", True),
+    "shade_taps": (0, 1, (-1, 2), "shade_taps must be 0 or 1", True),
+    "denoise_lds": (0, 1, (-1, 2), "denoise_lds must be 0 or 1", True),
+    "shade_batch": (1, 64, (0, 65), "shade_batch must be in [1, 64]", True),
+}
+READABLE = ("jit_active", "jit_tier_active", "jit_tier_seconds", "jit_seconds", "jit_trace_waves", "jit_shade_waves",
+            "kernel", "shade_batch", "bin_samples", "bin_chunks", "bin_fallback", "bin_sets", "bin_overflow",
+            "trace_launches", "shade_launches", "sky_launches", "display_ms", "guide_ms", "denoise_ms", "guides_valid",
+            "denoise_lds", "trace_ms", "shade_ms", "sky_ms", "bin_bytes", "bin_lanes", "bin_table", "shade_taps",
+            "jit_cache", "gen_trace", "gen_norec", "tap_stat_0")
+# per sample of a lane: two 64 B ray buffers, hit quad, bin key + binned slot, colour (c1: no wide masks)
+BYTES_PER_SAMPLE = 2 * 64 + 16 + 8 + 16
+
+
+def _tracer(options=None):
+    prog = scenes.SCENES["c1"]().compile(CompData())
+    return PathTracer(W, H, prog, settings=N.Settings(debug=0, bounces=BOUNCES, scale=1.0, fov=1.0, aabb=0),
+                      options=options)
+
+
+def _set(pt, key, value):
+    return N.lib().pt_set_option(pt._ctx, key.encode(), int(value))
+
+
+def _get(pt, key):
+    v = ctypes.c_double(float("nan"))
+    rc = N.lib().pt_get_option(pt._ctx, key.encode(), ctypes.byref(v))
+    return rc, v.value
+
+
+def _err(pt):
+    return N.lib().pt_last_error(pt._ctx).decode()
+
+
+@pytest.fixture(scope="module")
+def fresh():
+    """A context with c1 uploaded and nothing dispatched (the range tests only set and read options)."""
+    pt = _tracer()
+    yield pt
+    pt.close()
+
+
+@pytest.fixture(scope="module")
+def dispatched():
+    """(context, image) after one binned dispatch of SPP samples over LANES lanes on the tier-up kernel."""
+    pt = _tracer({"kernel": "binned", "bin_lanes": LANES})
+    pt.set_option("jit_wait", 1)
+    pt.dispatch(_constants(), SPP)
+    img = pt.read_image()
+    img.setflags(write=False)
+    yield pt, img
+    pt.close()
+
+
+def _constants():
+    return N.Constants(time=0.0, frame=1, aspect=1.0, last_clear=1)
+
+
+def test_fresh_context_readings():
+    pt = _tracer()
+    try:
+        for key in ("display_ms", "guide_ms", "denoise_ms", "trace_launches", "shade_launches", "sky_launches",
+                    "bin_chunks", "guides_valid"):
+            assert _get(pt, key) == (N.PT_OK, 0.0), key
+        for key in ("bin_sets", "bin_overflow"):
+            assert _get(pt, key) == (N.PT_OK, -1.0), key
+        ms = ctypes.c_float(0.0)
+        assert N.lib().pt_last_dispatch_ms(pt._ctx, ctypes.byref(ms)) == N.PT_ERR_STATE
+        assert _err(pt) == "no dispatch recorded"
+    finally:
+        pt.close()
+
+
+@pytest.mark.parametrize("key", sorted(SETTABLE))
+def test_settable_range(fresh, key):
+    lo, hi, refused, text, readable = SETTABLE[key]
+    pt = fresh
+    for v in (hi, lo):
+        assert _set(pt, key, v) == N.PT_OK, (key, v)
+        if readable:
+            assert _get(pt, key) == (N.PT_OK, float(v)), (key, v)
+    for v in refused:  # the lowest accepted value stays
+        assert _set(pt, key, v) == N.PT_ERR_INVALID, (key, v)
+        assert _err(pt) == text
+        if readable:
+            assert _get(pt, key) == (N.PT_OK, float(lo)), (key, v)
+
+
+def test_jit_wait_ignores_its_value(fresh):
+    for v in (-7, 0, 1, INT_MAX):
+        assert _set(fresh, "jit_wait", v) == N.PT_OK
+
+
+def test_settable_but_unreadable(fresh):
+    for key in ("jit", "jit_bake", "jit_wait"):
+        rc, _ = _get(fresh, key)
+        assert rc == N.PT_ERR_INVALID
+        assert _err(fresh) == "unknown option " + key
+
+
+def test_unknown_keys(fresh):
+    for key in ("no_such_option", "", "kernels", "tap_stat", "jit_active "):
+        assert _set(fresh, key, 1) == N.PT_ERR_INVALID
+        assert _err(fresh) == "unknown option " + key
+        rc, _ = _get(fresh, key)
+        assert rc == N.PT_ERR_INVALID
+        assert _err(fresh) == "unknown option " + key
+    for key in READABLE:  # a key of the other direction only is unknown too
+        if key not in SETTABLE:
+            assert _set(fresh, key, 1) == N.PT_ERR_INVALID
+            assert _err(fresh) == "unknown option " + key
+
+
+def test_tap_stat_index(fresh):
+    for k in (-1, N.PT_ST_COUNT):
+        rc, _ = _get(fresh, "tap_stat_%d" % k)
+        assert rc == N.PT_ERR_INVALID
+        assert _err(fresh) == "tap_stat index out of range"
+    assert _get(fresh, "tap_stat_0") == (N.PT_OK, 0.0)
+    assert _get(fresh, "tap_stat_%d" % (N.PT_ST_COUNT - 1)) == (N.PT_OK, 0.0)
+
+
+def test_after_binned_dispatch(dispatched):
+    pt, _ = dispatched
+    assert pt.get_option("jit_active") == 1.0 and pt.get_option("jit_tier_active") == 1.0, pt.jit_log()
+    assert pt.get_option("trace_launches") == LANES * (BOUNCES + 1)
+    assert pt.get_option("shade_launches") == pt.get_option("trace_launches")
+    assert pt.get_option("sky_launches") == 0.0
+    for key in ("trace_ms", "shade_ms"):
+        ms = pt.get_option(key)
+        assert math.isfinite(ms) and ms >= 0.0, key
+    assert pt.get_option("sky_ms") == 0.0
+    assert pt.get_option("bin_chunks") == 1.0
+    # SPP frames of 64 pixels over LANES lanes: each lane's buffers hold its share
+    bin_cap = W * H * ((SPP + LANES - 1) // LANES)
+    assert pt.get_option("bin_bytes") == bin_cap * LANES * BYTES_PER_SAMPLE
+    assert pt.get_option("bin_lanes") == LANES and pt.get_option("kernel") == 3.0
+    assert math.isfinite(pt.last_dispatch_ms()) and pt.last_dispatch_ms() >= 0.0
+
+
+def test_every_readable_key(dispatched):
+    pt, _ = dispatched
+    for key in READABLE:
+        rc, v = _get(pt, key)
+        assert rc == N.PT_OK, (key, _err(pt))
+        assert not math.isnan(v), key
+
+
+def test_jit_off_unloads_and_stays_bit_exact(dispatched):
+    """(last of the module: it leaves the shared context on the interpreter kernels)"""
+    pt, before = dispatched
+    pt.set_option("jit", 0)
+    assert pt.get_option("jit_active") == 0.0 and pt.get_option("jit_tier_active") == 0.0
+    assert pt.get_option("jit_cache") == -1.0
+    pt.clear()
+    pt.dispatch(_constants(), SPP)
+    after = pt.read_image()
+    assert np.array_equal(after.view(np.uint32), before.view(np.uint32))
+    assert pt.get_option("trace_launches") == LANES * (BOUNCES + 1)
