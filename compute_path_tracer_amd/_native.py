@@ -209,6 +209,21 @@ def lib() -> ctypes.CDLL:
     return L
 
 
+def scene_kernel_source(prog, data=None, baked: int = 0) -> str:
+    """The scene-kernel source generated for ``prog`` with ``data`` (default:
+    the program's own values), not compiled: ``pt_scene_kernel_source``'s
+    two-call pattern."""
+    import numpy as np
+
+    d = np.ascontiguousarray(prog.data if data is None else data, np.float32)
+    args = (prog.ops, prog.n_ops, prog.aabbs, prog.n_aabb, d.ctypes.data_as(POINTER(c_float)), len(d), int(baked))
+    n = c_size_t()
+    assert lib().pt_scene_kernel_source(*args, None, 0, ctypes.byref(n)) == PT_OK
+    buf = ctypes.create_string_buffer(n.value)
+    assert lib().pt_scene_kernel_source(*args, buf, n.value, ctypes.byref(n)) == PT_OK
+    return buf.value.decode()
+
+
 def check(fn: str, rc: int, ctx=None) -> None:
     if rc != PT_OK:
         msg = ""

@@ -118,6 +118,13 @@ float pt_bound_k(const std::vector<PtNode> &nodes) {
     return float(K * (1.0 + 0x1p-20));
 }
 
+bool pt_fast_bounds(const std::vector<PtAabb> &boxes) {
+    for (const PtAabb &b : boxes)
+        for (int k = 0; k < 3; ++k)
+            if (!pt_div_coord_ok(b.bmin[k]) || !pt_div_coord_ok(b.bmax[k])) return false;
+    return true;
+}
+
 int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, const float *data, uint32_t n,
               std::vector<PtNode> &nodes, std::vector<PtAabb> &boxes, std::vector<PtMat> &mats, std::string &err) {
     auto bad = [&](const char *msg) {

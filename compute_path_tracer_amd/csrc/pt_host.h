@@ -1,5 +1,6 @@
 // pt_host.h -- host-side internals shared by the runtime's host files (pt_runtime.hip, pt_bin_host.cpp,
-// pt_options.cpp, pt_derive.cpp) and pt_jit.cpp.
+// pt_options.cpp, pt_derive.cpp), the scene-kernel generator (pt_jit.cpp), the scene kernels' hipRTC build and
+// on-disk cache (pt_jit_build.cpp) and their loading and lifecycle (pt_jit_state.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +47,10 @@ int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, 
 // Margin constant of the map() bound; NaN: no bound.
 float pt_bound_k(const std::vector<PtNode> &nodes);
 
+// Every box coordinate lies inside the reciprocal guard (pt_div_coord_ok): bounds() may take its slab values from
+// reciprocal products (PtLaunch.fast_bounds).
+bool pt_fast_bounds(const std::vector<PtAabb> &boxes);
+
 // Scene-specialised kernels (hipRTC): a loaded code object and its kernels.
 enum PtJitFn {
     kJitRender,       // pt_wave_jit: the tile-resident wave kernel
@@ -66,6 +71,71 @@ enum PtJitFn {
     kJitShadeTC,
     kJitFnCount
 };
+// The binned trace and shade kernels are built for 8 waves per SIMD (<= 64
+// VGPRs); a kernel whose build spills is rebuilt at 7 (compile_with_fallback).
+// With 28 trace waves per CU beside the other pipeline's passes, 8 + 8
+// measured +1.5 % over 7 + 7 at 24 (DESIGN.md 5 history).
+constexpr int kJitWaves = 8;
+// the shade kernel's accepted spill, bytes per lane, before its 7-wave rebuild
+constexpr long kShadeSpillOk = 16;
+// The scene kernels, in the order the generated source defines them: what the generator emits for each
+// (`extern "C" __global__ __launch_bounds__(bounds) [waves] void name(param) { body; }`), the name pt_jit_load
+// looks up for `fn`, and, for the four kernels built to a register budget, the spill (scratch bytes per lane)
+// beyond which compile_with_fallback rebuilds with `fallback`.
+struct PtJitKernel {
+    PtJitFn fn;
+    const char *name, *bounds;
+    const char *waves;  // the waves-per-SIMD attribute macro (pt_jit.cpp emit_waves_macros), or nullptr
+    const char *param, *body;
+    long spill_ok;
+    const char *fallback;  // hipRTC option that lowers `waves` to 7, or nullptr: never rebuilt
+};
+inline constexpr PtJitKernel kJitKernels[] = {
+    {kJitRender, "pt_wave_jit", "64", "PT_WAVES", "PtLaunch L", "pt::wave_body<pt::JitMap, false>(L)", 0, nullptr},
+    {kJitRenderStats, "pt_wave_jit_stats", "64", nullptr, "PtLaunch L", "pt::wave_body<pt::JitMap, true>(L)", 0,
+     nullptr},
+    // PT_TT_N: the pass with the taps in it
+    {kJitTrace, "pt_bin_trace_jit", "64", "PT_TRACET_WAVES", "PtPass P", "pt::bin_trace_body<pt::JitMap, false>(P)",
+     0, "-DPT_TT_N=7"},
+    {kJitTraceStats, "pt_bin_trace_jit_stats", "64", nullptr, "PtPass P", "pt::bin_trace_body<pt::JitMap, true>(P)",
+     0, nullptr},
+    // normal taps in the shade pass (PtPass.taps_in_shade): march-only trace (PT_TW_N), shade with JitMapB taps
+    {kJitTraceM, "pt_bin_trace_m_jit", "64", "PT_TRACE_WAVES", "PtPass P",
+     "pt::bin_trace_body<pt::JitMap, false, false>(P)", 0, "-DPT_TW_N=7"},
+    {kJitTraceMStats, "pt_bin_trace_m_jit_stats", "64", nullptr, "PtPass P",
+     "pt::bin_trace_body<pt::JitMap, true, false>(P)", 0, nullptr},
+    // the first pass without a gen pass (PtPass gen_trace; PT_TG_N)
+    {kJitTraceG, "pt_bin_trace_g_jit", "64", "PT_TRACEG_WAVES", "PtPass P",
+     "pt::bin_trace_body<pt::JitMap, false, false, true, PT_CAMK_FIXED>(P)", 0, "-DPT_TG_N=7"},
+    // (C3's shade kernel spills 8 bytes per lane at 8 waves and keeps them; PT_SW_N)
+    {kJitShadeT, "pt_bin_shade_t_jit", "PT_BIN_BLOCK", "PT_SHADE_WAVES", "PtPass P",
+     "pt::bin_shade_body<pt::JitTaps, false, false, PT_CAMK_FIXED>(P)", kShadeSpillOk, "-DPT_SW_N=7"},
+    // the same two for a posed camera (pt_set_camera; pt_path.h PT_CAMK_*): the host launches
+    // pt_bin_shade_tc_jit for shade pass 0 only, the one pass that makes camera rays again
+    {kJitTraceGC, "pt_bin_trace_gc_jit", "64", "PT_POSED_WAVES", "PtPass P",
+     "pt::bin_trace_body<pt::JitMap, false, false, true, PT_CAMK_POSED>(P)", 0, nullptr},
+    {kJitShadeTC, "pt_bin_shade_tc_jit", "PT_BIN_BLOCK", "PT_POSED_WAVES", "PtPass P",
+     "pt::bin_shade_body<pt::JitTaps, false, false, PT_CAMK_POSED>(P)", 0, nullptr},
+    {kJitShadeTStats, "pt_bin_shade_t_jit_stats", "PT_BIN_BLOCK", nullptr, "PtPass P",
+     "pt::bin_shade_body<pt::JitTaps, true, false>(P)", 0, nullptr},
+    // camera rays with the scene's bounds() (straight-line slab tests)
+    {kJitGen, "pt_bin_gen_jit", "PT_BIN_BLOCK", nullptr, "PtPass P",
+     "pt::bin_gen_body<pt::JitTaps, false, PT_CAMK_FIXED>(P)", 0, nullptr},
+    {kJitGenC, "pt_bin_gen_c_jit", "PT_BIN_BLOCK", nullptr, "PtPass P",
+     "pt::bin_gen_body<pt::JitTaps, false, PT_CAMK_POSED>(P)", 0, nullptr},
+    {kJitGenStats, "pt_bin_gen_jit_stats", "PT_BIN_BLOCK", nullptr, "PtPass P",
+     "pt::bin_gen_body<pt::JitTaps, true>(P)", 0, nullptr},
+};
+static_assert(sizeof kJitKernels / sizeof kJitKernels[0] == kJitFnCount, "one kernel per PtJitFn");
+constexpr bool pt_jit_kernels_cover_every_fn() {
+    for (int f = 0; f < kJitFnCount; ++f) {
+        int n = 0;
+        for (const PtJitKernel &k : kJitKernels) n += k.fn == f;
+        if (n != 1) return false;
+    }
+    return true;
+}
+static_assert(pt_jit_kernels_cover_every_fn(), "each PtJitFn names exactly one kernel");
 struct PtJitModule {
     hipModule_t module = nullptr;
     hipFunction_t fn[kJitFnCount] = {};
@@ -86,6 +156,15 @@ hipFunction_t pt_jit_select(const PtJitModule &m, PtJitStage stage, bool stats, 
 // when a value changes).
 std::string pt_jit_source(const std::vector<PtNode> &nodes, const std::vector<PtAabb> &boxes, bool fast_bounds,
                           bool bake);
+// (program, data) -> the derived tables and the source generated for them (pt_jit_compile, pt_scene_kernel_source);
+// pt_derive's return code, `src` set on PT_OK
+struct PtDerived {
+    std::vector<PtNode> nodes;
+    std::vector<PtAabb> boxes;
+    std::vector<PtMat> mats;
+};
+int pt_derive_source(const pt_op *ops, uint32_t n_ops, const pt_aabb *aabbs, uint32_t n_aabb, const float *data,
+                     uint32_t n_data, bool bake, PtDerived &t, std::string &src, std::string &err);
 // Compile with hipRTC for gfx950; returns the code object or an error log.
 // on-disk cache first (*from_disk: the code object came from lib/jitcache)
 bool pt_jit_compile_source(const std::string &src, std::vector<char> &code, std::string &log, bool *from_disk = nullptr);
@@ -93,7 +172,7 @@ bool pt_jit_compile_source(const std::string &src, std::vector<char> &code, std:
 bool pt_jit_load(const std::vector<char> &code, PtJitModule &m, std::string &err);
 void pt_jit_unload(PtJitModule &m);
 
-// A context's scene kernels and their lifecycle (pt_jit.cpp).  A code object
+// A context's scene kernels and their lifecycle (pt_jit_state.cpp).  A code object
 // and where it came from: compiled by this process's hipRTC, or read from the
 // shipped on-disk cache (lib/jitcache)
 enum PtJitFrom { kJitCompiled = 0, kJitDisk = 1 };

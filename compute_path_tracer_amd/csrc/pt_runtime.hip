@@ -150,10 +150,7 @@ int pt_set_data(pt_ctx *c, const float *data, uint32_t n) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->prog.have_data = true;
     c->prog.bound_k = pt_bound_k(nodes);
-    c->prog.fast_bounds = true;
-    for (const PtAabb &b : boxes)
-        for (int k = 0; k < 3; ++k)
-            if (!pt_div_coord_ok(b.bmin[k]) || !pt_div_coord_ok(b.bmax[k])) c->prog.fast_bounds = false;
+    c->prog.fast_bounds = pt_fast_bounds(boxes);
     pt_jit_refresh(c->jit, nodes, boxes, c->prog.fast_bounds);
     return PT_OK;
 }

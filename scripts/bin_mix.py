@@ -7,7 +7,6 @@ boxes a 64-ray window drawn from one bin admits (the union of its rays'
 sets), against the per-ray popcount.  CPU only.
     python scripts/bin_mix.py
 """
-import ctypes
 import os
 import re
 import sys
@@ -17,11 +16,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from compute_path_tracer_amd import scenes, _native as N
 from compute_path_tracer_amd.sdf_editor import CompData
-prog = scenes.SCENES["c3"]().compile(CompData())
-args = (prog.ops, prog.n_ops, prog.aabbs, prog.n_aabb, prog.data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), len(prog.data), 1)
-n = ctypes.c_size_t(); N.lib().pt_scene_kernel_source(*args, None, 0, ctypes.byref(n))
-buf = ctypes.create_string_buffer(n.value); N.lib().pt_scene_kernel_source(*args, buf, n.value, ctypes.byref(n))
-src = buf.value.decode()
+src = N.scene_kernel_source(scenes.SCENES["c3"]().compile(CompData()), baked=1)
 boxes = []
 for m in re.finditer(r"constexpr PtAabb A(\d+)\{\{(.*?)\}, \{(.*?)\}, (\d+), 0\};", src):
     lo = [float.fromhex(t.strip().rstrip('f')) for t in m.group(2).split(',')]

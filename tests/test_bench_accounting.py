@@ -178,18 +178,9 @@ def test_executed_flops_drop_only_culled_work(counters):
 
 
 def _kernel_source(prog, data, baked: int) -> str:
-    import ctypes
-
     from compute_path_tracer_amd import _native as N
 
-    d = np.ascontiguousarray(data, np.float32)
-    args = (prog.ops, prog.n_ops, prog.aabbs, prog.n_aabb, d.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), len(d),
-            baked)
-    n = ctypes.c_size_t()
-    assert N.lib().pt_scene_kernel_source(*args, None, 0, ctypes.byref(n)) == N.PT_OK
-    buf = ctypes.create_string_buffer(n.value)
-    assert N.lib().pt_scene_kernel_source(*args, buf, n.value, ctypes.byref(n)) == N.PT_OK
-    return buf.value.decode()
+    return N.scene_kernel_source(prog, data, baked)
 
 
 @pytest.mark.parametrize("scene", ["c1", "c2", "c3"])

@@ -36,6 +36,23 @@ def _value(tok: str) -> float:
 def _baked(scene: str, tmp_path):
     """The values-baked scene kernel source (pt_scene_kernel_source: generated,
     not compiled) and its node literals."""
+    src = N.scene_kernel_source(scenes.SCENES[scene]().compile(CompData()), baked=1)
+    nodes = []
+    # the node literals of the first map (JitMap); JitMapB repeats them
+    for m in re.finditer(r"constexpr PtNode B(\d+)\{(.*?)\};\n", src[:src.index("struct JitMapB")]):
+        toks = [t for t in m.group(2).replace("{", ",").replace("}", ",").split(",") if t.strip()]
+        v = [_value(t) for t in toks]
+        nodes.append(dict(op=int(v[0]), shape=int(v[1]), combine=int(v[2]), inv=v[6], m=v[7:10], rot=v[10:16],
+                          size=v[16:19], pad=v[19]))
+        assert int(m.group(1)) == len(nodes) - 1
+    return src, nodes
+
+
+@pytest.mark.parametrize("scene", sorted(scenes.SCENES))
+def test_kernel_source_two_call_sizes(scene):
+    """pt_scene_kernel_source's two-call pattern: the first call reports the
+    bytes including the terminating NUL, a buffer one byte short is
+    PT_ERR_SIZE, and the full one holds exactly the reported text."""
     prog = scenes.SCENES[scene]().compile(CompData())
     args = (prog.ops, prog.n_ops, prog.aabbs, prog.n_aabb, prog.data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
             len(prog.data), 1)
@@ -46,15 +63,6 @@ def _baked(scene: str, tmp_path):
     assert N.lib().pt_scene_kernel_source(*args, buf, n.value, ctypes.byref(n)) == N.PT_OK
     src = buf.value.decode()
     assert len(src) + 1 == n.value
-    nodes = []
-    # the node literals of the first map (JitMap); JitMapB repeats them
-    for m in re.finditer(r"constexpr PtNode B(\d+)\{(.*?)\};\n", src[:src.index("struct JitMapB")]):
-        toks = [t for t in m.group(2).replace("{", ",").replace("}", ",").split(",") if t.strip()]
-        v = [_value(t) for t in toks]
-        nodes.append(dict(op=int(v[0]), shape=int(v[1]), combine=int(v[2]), inv=v[6], m=v[7:10], rot=v[10:16],
-                          size=v[16:19], pad=v[19]))
-        assert int(m.group(1)) == len(nodes) - 1
-    return src, nodes
 
 
 def _expected_shape_pad(n) -> float:
@@ -274,7 +282,7 @@ def _compile_log(scene: str) -> str:
 def test_spilling_build_falls_back_to_seven_waves(scene, fallback, tmp_path):
     """The scene kernels are built for 8 waves per SIMD (64 VGPRs); a build
     whose trace kernels spill, or whose shade kernel spills more than 16 bytes
-    per lane, is rebuilt at 7 (pt_jit.cpp pt_jit_compile_source).  C3 keeps
+    per lane, is rebuilt at 7 (pt_jit_build.cpp pt_jit_compile_source).  C3 keeps
     the 8-wave build; the 128-entry `wide` scene spills and falls back."""
     src, _ = _baked(scene, tmp_path)
     assert "#define PT_TW_N 8" in src and "#define PT_SW_N 8" in src
@@ -326,7 +334,7 @@ def _probe(scene: str, bake: str, first: str = "none", **env):
 
 
 def test_jit_disk_cache_round_trip(tmp_path):
-    """pt_jit.cpp's on-disk cache: PT_JIT_CACHE=2 writes one entry per
+    """pt_jit_build.cpp's on-disk cache: PT_JIT_CACHE=2 writes one entry per
     generated source, a later process reads the same code object back, and a
     compile knob that changes the build changes the key (a miss)."""
     d = str(tmp_path)
@@ -359,7 +367,7 @@ def test_shipped_scene_kernels_survive_a_torch_first_process():
 
 
 def test_wave_fallback_is_per_kernel():
-    """pt_jit.cpp rebuilds at 7 waves only the kernels whose 8-wave build
+    """pt_jit_build.cpp rebuilds at 7 waves only the kernels whose 8-wave build
     spilled (PT_TW_N: march-only trace, PT_TG_N: first pass, PT_TT_N: taps
     in the trace pass, PT_SW_N: shade beyond 16 bytes per lane); the log's
     first line names both lists, and they must agree.  C3's table build
