@@ -160,12 +160,25 @@ int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, 
         const float inv = 1.0f / s;  // `1.0 / data[scale]`
         d.inv = inv;
         for (int k = 0; k < 3; ++k) d.m[k] = data[op.position[k]] * inv;  // pos * (1.0 / s)
-        uint32_t f = 0;
-        if (inv != 1.0f) f |= PT_NF_SCALE;
-        if (d.m[0] != 0.0f || d.m[1] != 0.0f || d.m[2] != 0.0f) f |= PT_NF_POS;
         pt_sincos(data[op.rotation[0]], d.sx, d.cx);
         pt_sincos(data[op.rotation[1]], d.sy, d.cy);
         pt_sincos(data[op.rotation[2]], d.sz, d.cz);
+        // The reference multiplies by three full matrices (shapes.glsl:34-68),
+        // zeros included, and 0 * NaN = 0 * inf = NaN: one non-finite
+        // coordinate after the translation, or a NaN rotation about x or y,
+        // leaves all three coordinates NaN after the third matrix.  xform_f
+        // skips the zero terms, so it would keep the untouched coordinates
+        // finite.  A NaN translation makes them all NaN at once instead.  A
+        // NaN rotation about z, the last matrix, leaves a shape's z alone in
+        // both; a union hands (NaN, NaN, z) on to its children, whose own
+        // full matrices make z NaN too, so for a union it counts as well.
+        const bool z_nan = op.opcode == PT_OP_UNION_BEGIN && (!std::isfinite(d.sz) || !std::isfinite(d.cz));
+        if (!std::isfinite(inv) || !std::isfinite(d.m[0]) || !std::isfinite(d.m[1]) || !std::isfinite(d.m[2]) ||
+            !std::isfinite(d.sx) || !std::isfinite(d.cx) || !std::isfinite(d.sy) || !std::isfinite(d.cy) || z_nan)
+            d.m[0] = d.m[1] = d.m[2] = std::numeric_limits<float>::quiet_NaN();
+        uint32_t f = 0;
+        if (inv != 1.0f) f |= PT_NF_SCALE;
+        if (d.m[0] != 0.0f || d.m[1] != 0.0f || d.m[2] != 0.0f) f |= PT_NF_POS;
         if (!(d.cx == 1.0f && d.sx == 0.0f)) f |= PT_NF_RX;
         if (!(d.cy == 1.0f && d.sy == 0.0f)) f |= PT_NF_RY;
         if (!(d.cz == 1.0f && d.sz == 0.0f)) f |= PT_NF_RZ;

@@ -107,6 +107,10 @@ const Option kOptions[] = {
     // read only
     OPT_READ("jit_active", pt_jit_active(c->jit) ? 1.0 : 0.0),
     OPT_READ("jit_tier_active", c->jit.tier.module ? 1.0 : 0.0),
+    // what pt_set_data derived from the values (pt_derive.cpp): the map() bound's margin (NaN: no bound), and
+    // whether every box coordinate is inside bounds()' reciprocal guard
+    OPT_READ("bound_k", c->prog.bound_k),
+    OPT_READ("fast_bounds", c->prog.fast_bounds ? 1.0 : 0.0),
     OPT_READ("jit_tier_seconds", c->jit.tier_seconds),
     OPT_READ("jit_seconds", c->jit.seconds),
     OPT_READ("jit_trace_waves", jit_waves(c, PtJitStage::Trace, 64)),

@@ -357,6 +357,209 @@ def c3_no_aabb() -> SDFEditor:
     return ed
 
 
+def nan_cube(which: str = "position") -> SDFEditor:
+    """An emissive octahedron in front of a cube whose transform holds a NaN:
+    its position x ("position"), its rotation about x ("rotation": 2e7 is
+    beyond the range of the reference's sin / cos), or its
+    union's rotation about z with none of its own ("union-rotation").  The
+    reference multiplies by full rotation matrices, and 0 * NaN = NaN makes
+    all three of the cube's coordinates NaN; sdCube's min / max drop NaNs, so
+    its distance is 0 everywhere and every ray ends on it at once.  Kernels
+    that skip the matrices' zero terms keep a finite coordinate and see a slab
+    instead (found by random value edits on fuzz_scene(24); pt_derive.cpp
+    makes such a node's whole translation NaN)."""
+    a = _union("front", scale=2.0, pos=(0.0, 0.06, 0.07))
+    o = _shape(Shapes.OCTAHEDRON, pos=(-0.37, -0.65, 0.0), rot=(1.36, 1.46, -2.63), scale=0.64, size=(0.83,),
+               aabb=False, name="octahedron")
+    _mat(o, col=(0.72, 0.26, 0.28), brightness=1.6, spec=1.0, spec_col=(0.7, 0.68, 0.92), rough=0.3)
+    a.children_shapes.append(o)
+    b = _union("behind", pos=(0.19, 0.23, 0.47), rot=(-0.46, 0.0, 2e7 if which == "union-rotation" else 0.0))
+    nan = float("nan")
+    c = _shape(Shapes.CUBE, pos=(nan if which == "position" else 0.4, 0.8, 0.0),
+               rot={"rotation": (2e7, 0.0, 0.0), "union-rotation": (0.0, 0.0, 0.0)}.get(which, (-3.03, 0.0, 2.02)),
+               size=(0.61, 0.67, 0.65), aabb=False,
+               name="cube")
+    _mat(c, col=(0.59, 0.65, 0.91), brightness=3.8, light=(0.2, 0.5, 1.0), spec=0.35, rough=0.2)
+    b.children_shapes.append(c)
+    return SDFEditor([a, b])
+
+
+def nan_cube_rotation() -> SDFEditor:
+    return nan_cube("rotation")
+
+
+def nan_cube_union_rotation() -> SDFEditor:
+    return nan_cube("union-rotation")
+
+
+_FUZZ_KINDS = (Shapes.SPHERE, Shapes.CUBE, Shapes.TORUS, Shapes.OCTAHEDRON)
+FUZZ_DEEP_LEVELS = 8  # the interpreter's union stack (pt_device.h PT_MAX_DEPTH)
+
+
+def _fuzz_scale(rng, outside: bool) -> float:
+    """A scale: exactly 1 (p 0.4), the dyadic 0.5 or 2 (0.1 each), a
+    non-dyadic one in [0.6, 1.6] (0.25), and for unions (`outside`) 0.4 or 2.5
+    (0.15 together, 1/s outside [1/2, 2]; shapes get more non-dyadic ones)."""
+    r = rng.random()
+    if r < 0.4:
+        return 1.0
+    if r < 0.5:
+        return 0.5
+    if r < 0.6:
+        return 2.0
+    if r < 0.85 or not outside:
+        return float(rng.uniform(0.6, 1.6))
+    return 0.4 if rng.random() < 0.5 else 2.5
+
+
+def _fuzz_vec(rng, lo, hi, p_all: float, p_one: float):
+    """Three components from [lo[k], hi[k]]; all exactly 0 with p_all, else
+    each exactly 0 with p_one."""
+    v = [float(rng.uniform(lo[k], hi[k])) for k in range(3)]
+    zero_all = rng.random() < p_all
+    return tuple(0.0 if zero_all or rng.random() < p_one else x for x in v)
+
+
+def _fuzz_shape(rng, name: str, world: float, small: bool) -> Shape:
+    """One shape of about 0.5-1.8 world units (`world`: its ancestors' scale
+    product), or with p 0.2 a cube slab whose middle half-extent is 1.5-4 world
+    units (the scene kernels' one-face cube path); `small`: 0.6 of that, for
+    the later members of a Subtraction union."""
+    kind = _FUZZ_KINDS[int(rng.integers(4))]
+    sc = _fuzz_scale(rng, outside=False)
+    k = (0.6 if small else 1.0) / (sc * world)
+    if kind == Shapes.CUBE:
+        if rng.random() < 0.2:
+            size = [float(rng.uniform(1.5, 4.0)) / (sc * world), float(rng.uniform(1.5, 4.0)) / (sc * world),
+                    float(rng.uniform(0.1, 0.5)) / (sc * world)]
+            size = tuple(size[j] for j in rng.permutation(3))
+        else:
+            size = tuple(float(v) * k for v in rng.uniform(0.5, 1.6, 3))
+    elif kind == Shapes.TORUS:
+        size = (float(rng.uniform(0.9, 1.6)) * k, float(rng.uniform(0.25, 0.5)) * k)
+    else:
+        size = (float(rng.uniform(0.7, 1.8)) * k,)
+    pos = _fuzz_vec(rng, (-3.0 / world, -2.0 / world, -0.5 / world), (3.0 / world, 2.0 / world, 3.5 / world), 0.2, 0.15)
+    rot = _fuzz_vec(rng, (-math.pi,) * 3, (math.pi,) * 3, 0.2, 0.3)
+    s = _shape(kind, pos=pos, rot=rot, scale=sc, size=size, aabb=bool(rng.random() < 0.7), name=name,
+               ex=(1.0, 1.3, 2.0)[int(rng.integers(3))])
+    spec = (0.0, 0.0, float(rng.uniform(0.1, 0.9)), 1.0)[int(rng.integers(4))]
+    _mat(s, col=tuple(rng.uniform(0.1, 0.95, 3)), brightness=float(rng.uniform(1.5, 4.0)) if rng.random() < 0.35 else 0.0,
+         light=(1.0, 1.0, 1.0) if rng.random() < 0.5 else tuple(rng.uniform(0.3, 1.0, 3)), spec=spec,
+         spec_col=tuple(rng.uniform(0.6, 1.0, 3)), rough=float(rng.uniform(0.0, 0.6)))
+    return s
+
+
+def _fuzz_union(rng, name: str, depth: int, world: float, budget: list) -> Union:
+    """One union at nesting `depth` (1: a header union) with 0-2 child unions
+    down to depth 4 and 0-4 shapes; `budget[0]` caps the nodes still to make."""
+    ut = UnionType.SUBTRACTION if rng.random() < 0.3 else UnionType.UNION
+    sc = _fuzz_scale(rng, outside=True)
+    u = _union(name, ut, pos=_fuzz_vec(rng, (-0.5 / world,) * 3, (0.5 / world,) * 3, 0.35, 0.2),
+               rot=_fuzz_vec(rng, (-0.6,) * 3, (0.6,) * 3, 0.5, 0.3), scale=sc)
+    budget[0] -= 1
+    n_child = (0, 0, 0, 1, 1, 2)[int(rng.integers(6))] if depth < 4 else 0
+    n_shape = (0, 1, 2, 2, 3, 4)[int(rng.integers(6))]
+    for k in range(n_child):
+        if budget[0] > 0:
+            u.children_unions.append(_fuzz_union(rng, f"{name}.{k}", depth + 1, world * sc, budget))
+    for k in range(n_shape):
+        if budget[0] > 0:
+            budget[0] -= 1
+            u.children_shapes.append(_fuzz_shape(rng, f"{name}-{k}", world * sc,
+                                                 small=ut == UnionType.SUBTRACTION and k > 0))
+    return u
+
+
+def fuzz_scene(seed: int, profile: str = "mixed") -> SDFEditor:
+    """A random editor tree, the same for the same (seed, profile): values come
+    from np.random.default_rng(seed) only (the Floats' slot hashes are fresh
+    each time, as for every scene here, and reach no value).
+
+    profile "mixed": 1-5 header unions and at most 30 nodes (unions + shapes);
+    seeds whose draw stays at 12 program ops or fewer (a union counts two)
+    are the ones cheap enough to compile as scene kernels.  The distributions, per node:
+
+    * unions: Subtraction with p 0.3; 0-2 child unions (p 1/2, 1/3, 1/6) down to
+      nesting depth 4, and 0-4 shapes (p 1/6 for 0), so empty unions, unions
+      with only child unions (whose result survives) and unions whose first
+      shape overwrites their child unions (SURVEY.md A.9 (i)) all occur;
+    * shapes: the four kinds with equal chance, so each occurs as the first
+      (assign) member, as a later member of a Union and of a Subtraction union;
+    * scale: exactly 1 (p 0.4), 0.5, 2 (0.1 each), non-dyadic in [0.6, 1.6];
+      unions also 0.4 and 2.5 (p 0.15), outside [1/2, 2];
+    * position: all three components exactly 0 with p 0.2 (shapes) / 0.35
+      (unions), else each exactly 0 with p 0.15 / 0.2;
+    * rotation: all exactly 0 with p 0.2 (shapes) / 0.5 (unions), else each
+      exactly 0 with p 0.3 -- every PT_NF_* identity flag is set in some node
+      and clear in some;
+    * boxes: on with p 0.7, exaggeration 1.0, 1.3 or 2.0;
+    * cubes: half-extents of 0.5-1.6 world units, or (p 0.2) a slab with a
+      middle half-extent of 1.5-4 world units: both sides of fast_cube's threshold;
+    * materials: emitters with p 0.35 (brightness 1.5-4, light colour white or
+      random), and one direct shape of a header union is always an emitter
+      without a box (a lamp union is added when no header union has a shape),
+      so the image is lit;
+      specular chance 0 (p 1/2), fractional, or 1.
+
+    profile "deep": one chain of unions nested exactly FUZZ_DEEP_LEVELS deep,
+    one shape at every level, the same per-node distributions."""
+    rng = np.random.default_rng(seed)
+    if profile == "deep":
+        top, world, parent = None, 1.0, None
+        for d in range(FUZZ_DEEP_LEVELS):
+            budget = [1]
+            u = _fuzz_union(rng, f"deep-{d}", FUZZ_DEEP_LEVELS, world, budget)  # (transform and type only)
+            u.children_unions, u.children_shapes = [], [_fuzz_shape(rng, f"deep-{d}-0", world * u.transform.scale.val,
+                                                                    small=False)]
+            world *= u.transform.scale.val
+            if parent is None:
+                top = u
+            else:
+                parent.children_unions.append(u)
+            parent = u
+        unions = [top]
+    elif profile == "mixed":
+        budget = [30]
+        unions = []
+        for k in range(int(rng.integers(1, 6))):
+            if budget[0] > 0:
+                unions.append(_fuzz_union(rng, f"u{k}", 1, 1.0, budget))
+    else:
+        raise ValueError(f"unknown fuzz profile {profile!r}")
+    direct = [s for u in unions for s in u.children_shapes]
+    if not direct:
+        lamp = _union("lamp")
+        lamp.children_shapes.append(_shape(Shapes.SPHERE, pos=(float(rng.uniform(-1.0, 1.0)), 2.0, 1.0), size=(0.8,),
+                                           aabb=False, name="lamp"))
+        unions.append(lamp)
+        direct = lamp.children_shapes
+    lamp = direct[int(rng.integers(len(direct)))]
+    lamp.material.brightness.set(float(rng.uniform(1.5, 4.0)))
+    lamp.transform.aabb = False  # (a boxed shape of a nested graph can read a check[] entry bounds() never sets, and go dark)
+    return SDFEditor(unions)
+
+
+# Seeds of fuzz_scene(seed) for the interpreter kernels.  Chosen from 0..199:
+# every one renders a lit image (tests/test_scene_fuzz.py), and together they
+# hold every feature of fuzz_scene's docstring (the census there).
+FUZZ_SEEDS = (0, 2, 4, 5, 7, 8, 13, 17, 19, 20, 22, 23, 24, 28, 30, 31, 34, 35, 40, 41, 44, 45, 48, 49, 50, 51, 52, 53, 56, 58,
+              62, 64, 65, 66, 67, 70, 71, 73, 74, 75, 78, 84, 85, 86, 87, 88, 89, 93)
+# (seed, profile) of the scenes small enough to compile as scene kernels (at
+# most 12 program ops, a union counting two; the deep chain needs 24 by
+# construction): registered below as
+# "fuzz-<seed>", and build.py ships their kernels in lib/jitcache.
+FUZZ_JIT_SEEDS = ((56, "mixed"), (154, "mixed"), (259, "mixed"), (3521, "mixed"), (15793, "mixed"), (2, "deep"))
+
+
+def _fuzz_maker(seed: int, profile: str):
+    def make() -> SDFEditor:
+        return fuzz_scene(seed, profile)
+
+    make.__name__ = f"fuzz_scene_{seed}_{profile}"
+    return make
+
+
 SCENES = {
     "empty": empty,
     "c1": c1_default,
@@ -368,7 +571,11 @@ SCENES = {
     "cull": cull_stress,
     "tiny": tiny_union,
     "farbox": far_box,
+    "nan-position": nan_cube,
+    "nan-rotation": nan_cube_rotation,
+    "nan-union-rotation": nan_cube_union_rotation,
 }
+SCENES.update({f"fuzz-{seed}": _fuzz_maker(seed, profile) for seed, profile in FUZZ_JIT_SEEDS})
 
 # BASELINE.json configs -> (scene, width, height, spp, bounces)
 CONFIGS = {

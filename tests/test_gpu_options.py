@@ -39,7 +39,7 @@ READABLE = ("jit_active", "jit_tier_active", "jit_tier_seconds", "jit_seconds", 
             "kernel", "shade_batch", "bin_samples", "bin_chunks", "bin_fallback", "bin_sets", "bin_overflow",
             "trace_launches", "shade_launches", "sky_launches", "display_ms", "guide_ms", "denoise_ms", "guides_valid",
             "denoise_lds", "trace_ms", "shade_ms", "sky_ms", "bin_bytes", "bin_lanes", "bin_table", "shade_taps",
-            "jit_cache", "gen_trace", "gen_norec", "tap_stat_0")
+            "jit_cache", "gen_trace", "gen_norec", "tap_stat_0", "bound_k", "fast_bounds")
 # per sample of a lane: two 64 B ray buffers, hit quad, bin key + binned slot, colour (c1: no wide masks)
 BYTES_PER_SAMPLE = 2 * 64 + 16 + 8 + 16
 

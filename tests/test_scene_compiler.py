@@ -76,9 +76,10 @@ def test_topology_matches_captured_compiler_output():
         assert a["so_kind"] == (N.PT_SO_SCALAR if len(so) == 1 else N.PT_SO_VEC3)
 
 
-@pytest.mark.parametrize("name", ["c1", "c2", "c3", "nested", "empty"])
-def test_product_compiler_matches_oracle_restatement(name):
-    ed = scenes.SCENES[name]()
+def compiler_matches_oracle(ed: SDFEditor) -> None:
+    """The product compiler's data[], slots, check[] and box numbering against
+    the oracle's own restatement of SDFEditor::compile (also run over the
+    random scenes of test_scene_fuzz.py)."""
     rows = ed.rows()
     prog = ed.compile(CompData())
     osc = O.OracleScene(rows)
@@ -100,6 +101,11 @@ def test_product_compiler_matches_oracle_restatement(name):
     boxes = prog.aabb_dicts()
     assert sorted(a["back"] for a in boxes) == sorted(
         osc.node_slots(i)[2] for i, r in enumerate(rows) if r["kind"] != 0 and r["aabb"] and osc.node_slots(i)[2] >= 0)
+
+
+@pytest.mark.parametrize("name", ["c1", "c2", "c3", "nested", "empty"])
+def test_product_compiler_matches_oracle_restatement(name):
+    compiler_matches_oracle(scenes.SCENES[name]())
 
 
 def test_nested_quirks():
