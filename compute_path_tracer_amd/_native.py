@@ -51,6 +51,7 @@ SYMBOLS = (
     "pt_check_div_random", "pt_check_box_random", "pt_check_div_k", "pt_display", "pt_write_accum",
     "pt_compile_scene_keyed", "pt_save_rgba8", "pt_comm_size", "pt_traffic_probe", "pt_scene_kernel_source",
     "pt_set_camera", "pt_get_camera", "pt_set_sky", "pt_get_sky", "pt_render_guides", "pt_read_guides", "pt_denoise",
+    "pt_sample_field", "pt_mesh_extract", "pt_mesh_read",
 )
 PT_MATH = {"max": 0, "min": 1, "sqrt": 2, "sqrtf": 3, "sin": 4, "cos": 5, "div": 6, "fma": 7}
 
@@ -90,6 +91,25 @@ class DenoiseParams(Structure):
                 ("sigma_depth", c_float), ("sigma_albedo", c_float)]
 
 
+PT_MESH_BRICK, PT_MESH_MAX_CELLS, PT_MESH_MAX_PROJECT = 8, 1024, 8
+
+
+class MeshDesc(Structure):
+    """pt_mesh_desc: the grid, iso value and projection steps of ``pt_mesh_extract`` (new)."""
+
+    _fields_ = [("origin", c_float * 3), ("cell", c_float), ("cells", c_uint32 * 3), ("iso", c_float),
+                ("project", c_uint32)]
+
+
+class MeshInfo(Structure):
+    """pt_mesh_info: what ``pt_mesh_extract`` made and what it cost."""
+
+    _fields_ = [("n_vertices", c_uint32), ("n_triangles", c_uint32), ("clipped_edges", c_uint32),
+                ("void_cells", c_uint32), ("dropped_quads", c_uint32), ("bricks", c_uint32),
+                ("bricks_evaluated", c_uint32), ("reserved", c_uint32), ("corner_evals", c_uint64),
+                ("device_bytes", c_uint64)]
+
+
 class SceneNode(Structure):
     _fields_ = [
         ("kind", c_int32), ("parent", c_int32), ("union_type", c_int32), ("aabb", c_int32),
@@ -125,6 +145,7 @@ class Aabb(Structure):
 
 assert ctypes.sizeof(Constants) == 16 and ctypes.sizeof(Settings) == 20
 assert ctypes.sizeof(Camera) == 56 and ctypes.sizeof(Sky) == 52 and ctypes.sizeof(DenoiseParams) == 20
+assert ctypes.sizeof(MeshDesc) == 36 and ctypes.sizeof(MeshInfo) == 48
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
 
@@ -198,6 +219,9 @@ def lib() -> ctypes.CDLL:
         "pt_render_guides": (c_int, [ctx, POINTER(Constants), POINTER(Settings)]),
         "pt_read_guides": (c_int, [ctx, POINTER(c_float), POINTER(c_float), c_size_t]),
         "pt_denoise": (c_int, [ctx, POINTER(DenoiseParams), c_int, c_void_p, c_size_t]),
+        "pt_sample_field": (c_int, [ctx, POINTER(c_float), c_uint32, POINTER(c_float), POINTER(c_int32)]),
+        "pt_mesh_extract": (c_int, [ctx, POINTER(MeshDesc), POINTER(MeshInfo)]),
+        "pt_mesh_read": (c_int, [ctx, POINTER(c_float), POINTER(c_float), POINTER(c_int32), u32p, c_size_t, c_size_t]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("PT_LIB") and not hasattr(L, name):

@@ -182,6 +182,26 @@ struct pt_ctx {
         int lds = 1;  // pt_set_option "denoise_lds": LDS-staged taps at steps 1 and 2 (-19 % on five iterations: EXPERIMENTS.md)
         TimedSection guide_time, denoise_time;
     } dn;
+    // mesh export (pt_sample_field / pt_mesh_extract, pt_mesh_host.cpp): the extractor's
+    // working memory -- per brick: flag, slot, list; per evaluated brick: corner lattice, masks, counts and
+    // bases; per vertex: its cell; the counters -- and the last mesh, all grown on first use; the timing of the stages' kernels
+    struct Mesher {
+        DevBuf flag, slot, list, lattice, vmask, qmask, nv, nt, vbase, tbase, ctr, vcell;
+        DevBuf pos, nrm, shp, tri;       // the snapshot pt_mesh_read returns
+        DevBuf sample_xyz, sample_d, sample_shape;  // pt_sample_field's staging
+        bool have = false;               // a pt_mesh_extract succeeded
+        size_t n_vertices = 0, n_triangles = 0;
+        int skip = 1;  // pt_set_option "mesh_skip": 1 skips bricks by their centre value, 0 evaluates every brick
+        enum Stage { kSkip, kClassify, kScan, kEmit, kStages };
+        TimedSection stage_time[kStages], sample_time;
+        size_t bytes() const {
+            size_t n = 0;
+            for (const DevBuf *b : {&flag, &slot, &list, &lattice, &vmask, &qmask, &nv, &nt, &vbase, &tbase, &ctr, &vcell, &pos,
+                                    &nrm, &shp, &tri})
+                n += b->cap;
+            return n;
+        }
+    } mesh;
     struct Comm {
         ncclComm_t comm = nullptr;
         uint32_t nranks = 0;

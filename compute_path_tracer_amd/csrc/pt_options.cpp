@@ -76,6 +76,18 @@ int section_ms(pt_ctx *c, const TimedSection &t, bool sync, double *v) {
     return PT_OK;
 }
 
+// the stages of the last pt_mesh_extract, summed
+int mesh_ms(pt_ctx *c, double *v) {
+    *v = 0.0;
+    for (const TimedSection &t : c->mesh.stage_time) {
+        double ms = 0.0;
+        const int rc = section_ms(c, t, false, &ms);
+        if (rc != PT_OK) return rc;
+        *v += ms;
+    }
+    return PT_OK;
+}
+
 // summed over the dispatch's trace / shade / sky passes
 int log_ms(pt_ctx *c, EventLog &g, double *v) {
     HIPCHK(c, g.ms(v));
@@ -97,6 +109,7 @@ const Option kOptions[] = {
     OPT_INT("bin_table", bin.table, 0, 1, "bin_table must be 0 or 1"),
     OPT_INT("shade_taps", bin.shade_taps, 0, 1, "shade_taps must be 0 or 1"),
     OPT_INT("denoise_lds", dn.lds, 0, 1, "denoise_lds must be 0 or 1"),
+    OPT_INT("mesh_skip", mesh.skip, 0, 1, "mesh_skip must be 0 or 1"),
     // set only
     {"jit", FIELD(jit.enabled), 0, 1, "jit must be 0 or 1", set_jit, nullptr, false},
     {"jit_bake", FIELD(jit.bake), 0, 2, "jit_bake must be 0, 1 or 2", nullptr, nullptr, false},  // (at the next pt_set_data)
@@ -134,6 +147,13 @@ const Option kOptions[] = {
     OPT_GET("display_ms", section_ms(c, c->img.display_time, false, v)),
     OPT_GET("guide_ms", section_ms(c, c->dn.guide_time, true, v)),
     OPT_GET("denoise_ms", section_ms(c, c->dn.denoise_time, true, v)),
+    // the last pt_sample_field's kernel; the last pt_mesh_extract's kernels by stage (the extract waited for them)
+    OPT_GET("sample_ms", section_ms(c, c->mesh.sample_time, false, v)),
+    OPT_GET("mesh_skip_ms", section_ms(c, c->mesh.stage_time[pt_ctx::Mesher::kSkip], false, v)),
+    OPT_GET("mesh_classify_ms", section_ms(c, c->mesh.stage_time[pt_ctx::Mesher::kClassify], false, v)),
+    OPT_GET("mesh_scan_ms", section_ms(c, c->mesh.stage_time[pt_ctx::Mesher::kScan], false, v)),
+    OPT_GET("mesh_emit_ms", section_ms(c, c->mesh.stage_time[pt_ctx::Mesher::kEmit], false, v)),
+    OPT_GET("mesh_ms", mesh_ms(c, v)),
     OPT_READ("guides_valid", c->dn.guides_valid ? 1.0 : 0.0),
     OPT_GET("tap_stat_", tap_stat(c, key_, v)),
 };

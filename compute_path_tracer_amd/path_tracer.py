@@ -100,6 +100,97 @@ def sky_light(bottom, top=None, sun_direction=None, sun_color=(0.0, 0.0, 0.0), s
     return sky
 
 
+def mesh_grid(box_min, box_max, resolution: int):
+    """The grid ``extract_mesh`` lays over a box, in float32 steps: cubic cells
+    of edge cell = max(box_max - box_min) / resolution, so the longest axis
+    gets ``resolution`` cells and every other axis ceil(extent / cell) (at
+    least 1); origin = box_min.  Returns (origin float32[3], cell float32,
+    cells (nx, ny, nz)).  Host arithmetic only (no context)."""
+    F = np.float32
+    lo, hi = np.asarray(box_min, dtype=F), np.asarray(box_max, dtype=F)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError(f"box corners must be three finite numbers each, got {box_min!r}, {box_max!r}")
+    ext = hi - lo
+    if not (ext > 0).all():
+        raise ValueError(f"box_max must exceed box_min on every axis, got {box_min!r}, {box_max!r}")
+    if not 1 <= int(resolution) <= N.PT_MESH_MAX_CELLS:
+        raise ValueError(f"resolution must lie in [1, {N.PT_MESH_MAX_CELLS}], got {resolution!r}")
+    cell = F(ext.max() / F(int(resolution)))
+    cells = tuple(int(min(N.PT_MESH_MAX_CELLS, max(1, np.ceil(e / cell)))) for e in ext)
+    return lo, cell, cells
+
+
+class Mesh:
+    """A triangle mesh as ``PathTracer.extract_mesh`` returns it: ``positions``
+    and ``normals`` float32 [n][3], ``shapes`` int32 [n] (ordinal of the
+    program's SHAPE op whose material map() returns at the vertex, -1 = none),
+    ``triangles`` uint32 [m][3] wound outward, ``info`` the extractor's counts
+    (a dict of pt_mesh_info's fields)."""
+
+    def __init__(self, positions, normals, shapes, triangles, info=None):
+        self.positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        self.normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        self.shapes = np.ascontiguousarray(shapes, np.int32).reshape(-1)
+        self.triangles = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+        self.info = dict(info or {})
+
+    def vertex_colors(self, program: Program, data: Optional[np.ndarray] = None) -> np.ndarray:
+        """Each vertex's albedo, float32 [n][3]: the first three material slots
+        of its shape op in ``data`` (default: the program's own values); MDEF's
+        black where no shape claims the vertex."""
+        d = np.asarray(program.data if data is None else data, np.float32)
+        slots = [list(program.ops[i].material[:3]) for i in range(program.n_ops)
+                 if program.ops[i].opcode == N.PT_OP_SHAPE]
+        table = np.zeros((len(slots) + 1, 3), np.float32)  # row 0: shape -1
+        for k, s in enumerate(slots):
+            table[k + 1] = d[s]
+        if len(self.shapes) and (self.shapes.min() < -1 or self.shapes.max() >= len(slots)):
+            raise ValueError("mesh shape ordinal outside the program's shape ops")
+        return table[self.shapes + 1]
+
+    def save_obj(self, path: str) -> None:
+        """Wavefront OBJ: ``v``, ``vn`` and ``f a//a b//b c//c`` records (1-based)."""
+        with open(path, "w") as f:
+            f.write("# compute_path_tracer_amd mesh export\n")
+            for p in self.positions:
+                f.write("v %.9g %.9g %.9g\n" % tuple(float(x) for x in p))
+            for n in self.normals:
+                f.write("vn %.9g %.9g %.9g\n" % tuple(float(x) for x in n))
+            for t in self.triangles:
+                a, b, c = (int(i) + 1 for i in t)
+                f.write(f"f {a}//{a} {b}//{b} {c}//{c}\n")
+
+    def save_ply(self, path: str, colors: Optional[np.ndarray] = None) -> None:
+        """Binary little-endian PLY: x y z nx ny nz per vertex (+ uchar red
+        green blue from ``colors``, float [n][3] in 0..1), a uchar count and
+        three int32 indices per face."""
+        nv, nt = len(self.positions), len(self.triangles)
+        fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header = ["ply", "format binary_little_endian 1.0", "comment compute_path_tracer_amd mesh export",
+                  f"element vertex {nv}"] + [f"property float {n}" for n, _ in fields]
+        if colors is not None:
+            col = np.asarray(colors, np.float32)
+            if col.shape != (nv, 3):
+                raise ValueError(f"colors must be ({nv}, 3), got {col.shape}")
+            fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+            header += ["property uchar red", "property uchar green", "property uchar blue"]
+        header += [f"element face {nt}", "property list uchar int vertex_indices", "end_header"]
+        v = np.zeros(nv, dtype=np.dtype(fields))
+        for k, name in enumerate(("x", "y", "z")):
+            v[name] = self.positions[:, k]
+            v["n" + name] = self.normals[:, k]
+        if colors is not None:
+            c8 = np.rint(np.clip(np.nan_to_num(col), 0.0, 1.0) * 255.0).astype(np.uint8)
+            v["red"], v["green"], v["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
+        fc = np.zeros(nt, dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+        fc["n"] = 3
+        fc["i"] = self.triangles.astype(np.int32)
+        with open(path, "wb") as f:
+            f.write(("\n".join(header) + "\n").encode("ascii"))
+            f.write(v.tobytes())
+            f.write(fc.tobytes())
+
+
 class PathTracer:
     def __init__(self, width: int, height: int, program: Optional[Program] = None, data: Optional[np.ndarray] = None,
                  device: int = 0, settings: Optional[N.Settings] = None, options: Optional[dict] = None):
@@ -372,6 +463,45 @@ class PathTracer:
         self._chk("pt_denoise", self._L.pt_denoise(self._ctx, ctypes.byref(p), self.DENOISE_OUTPUTS[output],
                                                     out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
         return out
+
+    # -- mesh export (new: field sampling and a surface-nets extractor) -------
+    def sample_field(self, points):
+        """pt_sample_field: map() at ``points`` (float [n][3]) with every
+        check[] entry true.  Returns (d float32 [n], shape int32 [n]): the
+        distance, and the ordinal of the SHAPE op whose material map() returns
+        there (-1 = none)."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        d, s = np.empty(len(p), np.float32), np.empty(len(p), np.int32)
+        self._chk("pt_sample_field", self._L.pt_sample_field(
+            self._ctx, p.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), len(p),
+            d.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return d, s
+
+    def extract_mesh(self, box_min=None, box_max=None, resolution: int = 128, iso: float = 0.0, project: int = 2,
+                     grid=None) -> Mesh:
+        """pt_mesh_extract + pt_mesh_read: the surface map(p) = ``iso`` inside
+        the box as a triangle mesh (surface nets on mesh_grid's cubic cells,
+        ``project`` Newton steps per vertex).  ``grid`` = (origin, cell, cells)
+        gives the grid itself instead of a box.  The mesh is a snapshot; the
+        image, guides, camera, sky and options are untouched."""
+        origin, cell, cells = grid if grid is not None else mesh_grid(box_min, box_max, resolution)
+        desc = N.MeshDesc(cell=float(cell), iso=float(iso), project=int(project))
+        for k in range(3):
+            desc.origin[k], desc.cells[k] = float(origin[k]), int(cells[k])
+        info = N.MeshInfo()
+        self._chk("pt_mesh_extract", self._L.pt_mesh_extract(self._ctx, ctypes.byref(desc), ctypes.byref(info)))
+        return self.read_mesh({name: int(getattr(info, name)) for name, _ in N.MeshInfo._fields_})
+
+    def read_mesh(self, info: dict) -> Mesh:
+        """pt_mesh_read: the last extracted mesh; ``info`` as extract_mesh made it (its counts size the arrays)."""
+        nv, nt = info["n_vertices"], info["n_triangles"]
+        pos, nrm = np.empty((nv, 3), np.float32), np.empty((nv, 3), np.float32)
+        shp, tri = np.empty(nv, np.int32), np.empty((nt, 3), np.uint32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        self._chk("pt_mesh_read", self._L.pt_mesh_read(
+            self._ctx, pos.ctypes.data_as(fp), nrm.ctypes.data_as(fp), shp.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            tri.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), nv, nt))
+        return Mesh(pos, nrm, shp, tri, info)
 
     # -- RCCL ------------------------------------------------------------
     @staticmethod

@@ -321,6 +321,55 @@ typedef struct {                 /* 20 bytes */
 #define PT_DENOISE_LINEAR 2
 #define PT_DENOISE_MAX_ITERATIONS 8
 int pt_denoise(pt_ctx *ctx, const pt_denoise_params *p, int format, void *out, size_t bytes);
+/* Mesh export (new; DESIGN.md 3.27 has the f32 steps and the orders).
+ * Field sampling: map() at n caller points (xyz, 3 floats each) with every
+ * check[] entry true (no bounds() cull).  d[i] = distance, shape[i] = ordinal
+ * of the PT_OP_SHAPE op whose material map() returns (Hit.m - 1), -1 = none
+ * (MDEF).  A point with a non-finite coordinate is mapped as (NaN, NaN, NaN),
+ * which is what the reference's full rotation matrices make of it.  Either
+ * output may be NULL.  Blocking.  n = 0 is a no-op.  PT_ERR_STATE without
+ * program or data. */
+int pt_sample_field(pt_ctx *ctx, const float *xyz, uint32_t n, float *d, int32_t *shape);
+/* Surface-nets mesh of {p : map(p) = iso} on a caller-given grid of cubic
+ * cells: one vertex per cell the surface crosses (the mean of the crossings
+ * on its edges, then `project` Newton steps along the normal, clamped into
+ * the cell), one quad (two triangles, wound outward) per interior grid edge
+ * whose endpoints differ in sign. */
+#define PT_MESH_BRICK 8        /* cells per brick edge: the unit of the skip test and of the vertex order */
+#define PT_MESH_MAX_CELLS 1024 /* per axis */
+#define PT_MESH_MAX_PROJECT 8
+typedef struct {          /* 36 bytes */
+    float origin[3];      /* grid corner (0,0,0) */
+    float cell;           /* edge length, finite, > 0 */
+    uint32_t cells[3];    /* 1..1024 per axis */
+    float iso;            /* inside <=> map(p) < iso; 0 = the scene's surface */
+    uint32_t project;     /* 0..8 projection steps per vertex */
+} pt_mesh_desc;
+typedef struct {          /* 48 bytes */
+    uint32_t n_vertices, n_triangles;
+    uint32_t clipped_edges;    /* sign-changing edges on the grid's boundary: emit nothing; > 0 = the box cuts the surface */
+    uint32_t void_cells;       /* cells with a non-finite corner value: no vertex */
+    uint32_t dropped_quads;    /* interior sign-changing edges next to a void cell */
+    uint32_t bricks, bricks_evaluated;   /* 8x8x8-cell bricks (PT_MESH_BRICK 8); evaluated = not skipped */
+    uint32_t reserved;         /* 0 */
+    uint64_t corner_evals;     /* map() calls on grid corners (skip tests not counted) */
+    uint64_t device_bytes;     /* working memory held by the extractor */
+} pt_mesh_info;
+/* Blocking; the result stays in the context, a snapshot that pt_mesh_read
+ * returns until the next pt_mesh_extract or pt_destroy (scene edits do not
+ * invalidate it).  The accumulation image, guides, camera, sky and options
+ * are untouched.  PT_ERR_INVALID (the previous mesh stays) for a NULL
+ * argument, a non-finite origin / cell / iso, cell <= 0, a cells[] entry
+ * outside 1..1024 or project > 8; PT_ERR_STATE without program or data;
+ * PT_ERR_UNSUPPORTED if vertices or triangles would reach 2^31. */
+int pt_mesh_extract(pt_ctx *ctx, const pt_mesh_desc *g, pt_mesh_info *info);
+/* The last extracted mesh: positions and normals 3 floats per vertex, shapes
+ * one ordinal per vertex (as pt_sample_field's), triangles 3 vertex indices
+ * each; the caps count vertices and triangles.  Any pointer may be NULL.
+ * Blocking.  PT_ERR_STATE before any extract; PT_ERR_SIZE (nothing written) if
+ * a cap is too small for an array that is asked for. */
+int pt_mesh_read(pt_ctx *ctx, float *positions, float *normals, int32_t *shapes, uint32_t *triangles,
+                 size_t vertex_cap, size_t triangle_cap);
 /* Tuning knobs: "kernel" (0 auto = 3, 1 simple one-path-per-lane, 2 tile-
  * resident wavefront state machine, 3 mask-binned passes: per bounce, the
  * rays of a chunk of frames are grouped by their bounds() check set before
@@ -345,7 +394,9 @@ int pt_denoise(pt_ctx *ctx, const pt_denoise_params *p, int format, void *out, s
  * while the values stay unchanged) and "jit_wait" (block until a pending
  * tier-up build is installed) and "denoise_lds" (pt_denoise: 1, the default,
  * stages a block's tile and halo in LDS for the iterations of step 1 and 2;
- * 0 loads every tap directly).  Results are bit-identical for every value. */
+ * 0 loads every tap directly) and "mesh_skip" (pt_mesh_extract: 1, the
+ * default, skips a brick whose centre value proves it holds no surface; 0
+ * evaluates every brick).  Results are bit-identical for every value. */
 int pt_set_option(pt_ctx *ctx, const char *key, int value);
 /* Read back: "jit_active" (1 when the scene-specialised kernel is loaded),
  * "jit_seconds" (last hipRTC compile time), "jit_tier_active" /
@@ -359,7 +410,10 @@ int pt_set_option(pt_ctx *ctx, const char *key, int value);
  * "sky_launches" (the same for its sky passes, pt_set_sky; 0 without a sky), "display_ms"
  * (device time of the last pt_display's kernel), "guide_ms" / "denoise_ms"
  * (device time of the last pt_render_guides' kernel / of all iterations of the
- * last pt_denoise, without its display pass), "guides_valid", "gen_trace" / "gen_norec"
+ * last pt_denoise, without its display pass), "mesh_skip", "sample_ms" (the
+ * last pt_sample_field's kernel), "mesh_ms" (the last pt_mesh_extract's
+ * kernels, the sum of "mesh_skip_ms", "mesh_classify_ms", "mesh_scan_ms" and
+ * "mesh_emit_ms"), "guides_valid", "gen_trace" / "gen_norec"
  * (the last timed binned dispatch's first pass made its own camera rays /
  * and stored no ray records for shade pass 0). */
 int pt_get_option(pt_ctx *ctx, const char *key, double *value);
