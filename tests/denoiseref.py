@@ -1,8 +1,8 @@
 """CPU reference of the denoiser (test infrastructure).
 
-guides(): the first-hit guide images, built as camref builds its debug views
--- camref.camera_ray with the aperture set to 0 over the jitter-free screen
-point, CamScene.bounds, pyref.cast_ray / calc_normal.
+guides(): the first-hit guide images, built as pyref builds its debug views
+-- pyref.camera_ray with the aperture set to 0 over the jitter-free screen
+point, camref.CamScene.bounds, pyref.cast_ray / calc_normal.
 
 atrous(): the edge-stopping a-trous wavelet in numpy float32, whole-image
 elementwise operations per tap in the contract's loop order (dy outer, dx
@@ -24,7 +24,7 @@ def guides(rows, w, h, aspect, fov=1.0, camera=None):
     """(g0, g1), float32 (h, w, 4) each: g0 = (n, t), g1 = (albedo, 1) on a hit,
     g0 = (0, 0, 0, t), g1 = 0 on a miss.  `camera`: a Camera struct or None."""
     sc = camref.CamScene(rows)
-    cam = camref.camera_fields(camera)
+    cam = P.camera_fields(camera)
     if cam is not None:  # a lens as its pinhole: no lens draw, no rng at all
         cam = cam[:4] + (F(0.0), cam[5])
     aspect, fov = F(aspect), F(fov)
@@ -35,7 +35,7 @@ def guides(rows, w, h, aspect, fov=1.0, camera=None):
             for x in range(w):
                 ux = ((F(x) / F(w)) * F(2.0) - F(1.0)) * aspect
                 uy = (F(y) / F(h)) * F(2.0) - F(1.0)
-                ro, rd = camref.camera_ray(cam, ux, uy, fov, None)
+                ro, rd = P.camera_ray(cam, ux, uy, fov, None)
                 check, _ = sc.bounds(ro, rd)
                 t, m = P.cast_ray(sc, ro, rd, check)
                 g0[y, x, 3] = t

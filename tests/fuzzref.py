@@ -9,7 +9,7 @@ import numpy as np
 
 from compute_path_tracer_amd import _native as N, scenes
 from compute_path_tracer_amd.sdf_editor import CompData
-from oracle import oracle as O
+from gpuharness import aspect, first_difference, oracle_image, pixels_changed  # noqa: F401 (used as R.<name>)
 
 # the size every random scene is rendered at on the GPU
 W, H, SPP, BOUNCES = 24, 16, 2, 4
@@ -18,37 +18,12 @@ KINDS = {N.PT_NODE_SPHERE: "sphere", N.PT_NODE_CUBE: "cube", N.PT_NODE_TORUS: "t
 ROLES = {N.PT_COMBINE_ASSIGN: "first", N.PT_COMBINE_UNION: "union-member", N.PT_COMBINE_SUBTRACTION: "sub-member"}
 
 
-def aspect(w, h):
-    return float(np.float32(w) / np.float32(h))
-
-
-def oracle_image(ed, w, h, spp, bounces, counters=False):
-    return O.OracleScene(ed.rows()).render(w, h, O.Constants(0.0, 1, aspect(w, h), 1),
-                                           O.Settings(0, bounces, 1.0, 1.0, 0), spp, counters=counters)
-
-
 @functools.lru_cache(maxsize=None)
 def fuzz_oracle(seed, profile="mixed", w=W, h=H, spp=SPP, bounces=BOUNCES):
     """The oracle's image of fuzz_scene(seed, profile), computed once and shared (read-only)."""
     img = oracle_image(scenes.fuzz_scene(seed, profile), w, h, spp, bounces)
     img.setflags(write=False)
     return img
-
-
-def first_difference(got, want):
-    """None when the images agree bit for bit (a NaN equal only to a NaN in
-    the same place), else "(x, y): got ... want ..." of the first texel that differs."""
-    same = (got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))
-    bad = np.argwhere(~same.all(-1))
-    if not len(bad):
-        return None
-    y, x = (int(v) for v in bad[0])
-    return f"{len(bad)} texels differ, first (x={x}, y={y}): got {got[y, x].tolist()} want {want[y, x].tolist()}"
-
-
-def pixels_changed(a, b):
-    """Pixels whose bits differ between two oracle images."""
-    return int((a.view(np.uint32) != b.view(np.uint32)).any(-1).sum())
 
 
 def _literal(tok):

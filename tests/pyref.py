@@ -339,7 +339,73 @@ def calc_normal(sc, p, check):
 PI2 = F(2.0) * F(3.14159265359)
 
 
-def path_trace(sc, ro, rd, rng, bounces, debug):
+# ------------------------------------------------------- camera and sky
+def camera_fields(cam):
+    """A Camera (ctypes) or None -> (origin, right, up, forward, aperture, focus) in float32, or None."""
+    if cam is None:
+        return None
+    return ([F(v) for v in cam.origin], [F(v) for v in cam.right], [F(v) for v in cam.up],
+            [F(v) for v in cam.forward], F(cam.aperture), F(cam.focus))
+
+
+def camera_ray(cam, ux, uy, fov, rng):
+    """(ro, rd) of screen point (ux, uy); draws the lens's two numbers from rng."""
+    if cam is None:  # the reference's fixed camera
+        return [F(0.0), F(0.0), F(-3.0)], normalize([ux, uy, fov])
+    origin, right, up, fwd, aperture, focus = cam
+    rd = normalize([(right[k] * ux + up[k] * uy) + fwd[k] * fov for k in range(3)])
+    ro = list(origin)
+    if aperture > F(0.0):
+        u1 = rng.f01()
+        u2 = rng.f01()
+        r = F(np.sqrt(u1)) * aperture
+        a = u2 * PI2
+        sa, ca = sincos(a)
+        lx = r * ca
+        ly = r * sa
+        pf = [origin[k] + rd[k] * focus for k in range(3)]
+        ro = [(origin[k] + right[k] * lx) + up[k] * ly for k in range(3)]
+        rd = normalize([pf[k] - ro[k] for k in range(3)])
+    return ro, rd
+
+
+def primary_ray(cam, x, y, frame, w, h, aspect, fov):
+    """(ro, rd, rng) of pixel (x, y) in `frame`: gen_rng, jitter, calc_uv, camera."""
+    rng = Rng(gen_rng(x, y, frame, w, h))
+    jx = rng.f01() - F(0.5)
+    jy = rng.f01() - F(0.5)
+    ux = ((F(x) + jx) / F(w)) * F(2.0) - F(1.0)
+    uy = ((F(y) + jy) / F(h)) * F(2.0) - F(1.0)
+    ux = ux * aspect
+    ro, rd = camera_ray(cam, ux, uy, fov, rng)
+    return ro, rd, rng
+
+
+def sky_fields(sky):
+    """A Sky (ctypes) or None -> (bottom, top, sun_dir, sun_color, sun_cos) in float32, or None."""
+    if sky is None:
+        return None
+    return ([F(v) for v in sky.bottom], [F(v) for v in sky.top], [F(v) for v in sky.sun_dir],
+            [F(v) for v in sky.sun_color], F(sky.sun_cos))
+
+
+def sky_radiance(sky, rd):
+    """(g, in_sun): the sky's radiance along rd, in the f32 steps of DESIGN.md 3.25."""
+    bottom, top, sun_dir, sun_color, sun_cos = sky
+    t = rd[1] * F(0.5) + F(0.5)
+    g = [bottom[k] + (top[k] - bottom[k]) * t for k in range(3)]
+    s = (rd[0] * sun_dir[0] + rd[1] * sun_dir[1]) + rd[2] * sun_dir[2]
+    in_sun = bool(s >= sun_cos)
+    if in_sun:
+        g = [g[k] + sun_color[k] for k in range(3)]
+    return g, in_sun
+
+
+# ------------------------------------------------------------ the path
+def path_trace(sc, ro, rd, rng, bounces, debug, sky=None, counts=None):
+    """One sample's path.  With a sky (sky_fields), a segment that misses adds
+    sky_radiance(rd) * thr (debug 0 only) before the path ends; the sky draws
+    no random number.  counts, when given: {"miss", "sun"} tallies."""
     ret = [F(0)] * 3
     thr = [F(1)] * 3
     i = 0
@@ -347,6 +413,13 @@ def path_trace(sc, ro, rd, rng, bounces, debug):
         check, _ = sc.bounds(ro, rd)
         t, m = cast_ray(sc, ro, rd, check)
         if t > F(100.0):
+            if counts is not None:
+                counts["miss"] += 1
+            if sky is not None and debug == 0:
+                g, in_sun = sky_radiance(sky, rd)
+                if counts is not None:
+                    counts["sun"] += int(in_sun)
+                ret = [ret[k] + g[k] * thr[k] for k in range(3)]
             break
         hp = [ro[k] + rd[k] * t for k in range(3)]
         n = calc_normal(sc, hp, check)
@@ -384,24 +457,28 @@ def path_trace(sc, ro, rd, rng, bounces, debug):
     return ret
 
 
-def render(rows, w, h, frame, last_clear, aspect, bounces, spp, debug=0, fov=1.0, image=None):
-    sc = Scene(rows)
+def render_scene(sc, w, h, frame, last_clear, aspect, bounces, spp, debug=0, fov=1.0, camera=None, sky=None,
+                 counts=None, image=None):
+    """`spp` frames from `frame` of a built scene (a Scene, or one with the
+    same map() and bounds()), mixed into `image` (None: a cleared one).
+    camera: a Camera struct (None: the reference's fixed camera).  sky: a Sky
+    struct (None: the reference's void).  counts, when given, receives the
+    samples whose path ended in a miss ("miss") and those of them inside the
+    sun's disc ("sun")."""
+    cam = camera_fields(camera)
+    sk = sky_fields(sky)
+    if counts is not None:
+        counts.update(miss=0, sun=0)
     img = np.zeros((h, w, 4), np.float32) if image is None else image
+    fov, aspect = F(fov), F(aspect)
     with np.errstate(all="ignore"):
         for y in range(h):
             for x in range(w):
                 for j in range(spp):
-                    rng = Rng(gen_rng(x, y, frame + j, w, h))
-                    jx = rng.f01() - F(0.5)
-                    jy = rng.f01() - F(0.5)
-                    ux = ((F(x) + jx) / F(w)) * F(2.0) - F(1.0)
-                    uy = ((F(y) + jy) / F(h)) * F(2.0) - F(1.0)
-                    ux = ux * F(aspect)
-                    rd = normalize([ux, uy, F(fov)])
-                    ro = [F(0.0), F(0.0), F(-3.0)]
+                    ro, rd, rng = primary_ray(cam, x, y, frame + j, w, h, aspect, fov)
                     if debug in (0, 3):
-                        col = path_trace(sc, ro, rd, rng, bounces, debug)
-                    elif debug == 1:
+                        col = path_trace(sc, ro, rd, rng, bounces, debug, sk, counts)
+                    elif debug == 1:  # (views 1 and 2 never path trace: no sky, no counts)
                         check, dbg = sc.bounds(ro, rd)
                         t, m = cast_ray(sc, ro, rd, check)
                         if t > F(100.0):
@@ -425,3 +502,8 @@ def render(rows, w, h, frame, last_clear, aspect, bounces, spp, debug=0, fov=1.0
                             px[k] = F(px[k]) * (F(1.0) - wgt) + F(col[k]) * wgt
                     px[3] = F(1.0)
     return img
+
+
+def render(rows, w, h, frame, last_clear, aspect, bounces, spp, debug=0, fov=1.0, image=None):
+    """The reference's render, on the pure-Python Scene."""
+    return render_scene(Scene(rows), w, h, frame, last_clear, aspect, bounces, spp, debug, fov, image=image)

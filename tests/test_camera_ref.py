@@ -6,14 +6,11 @@ import numpy as np
 import pytest
 
 import camref
+import gpuharness as G
 from compute_path_tracer_amd import scenes
 from oracle import oracle as O
 
 F = np.float32
-
-
-def _aspect(w, h):
-    return float(F(w) / F(h))
 
 
 @pytest.mark.parametrize("name,w,h,spp,bounces", [
@@ -25,7 +22,7 @@ def _aspect(w, h):
 def test_camref_default_camera_equals_oracle(name, w, h, spp, bounces):
     """camref's render loop with the default camera is pto_render, bit for bit."""
     rows = scenes.SCENES[name]().rows()
-    a = _aspect(w, h)
+    a = G.aspect(w, h)
     got = camref.render(rows, w, h, 1, 1, a, bounces, spp)
     ref = O.OracleScene(rows).render(w, h, O.Constants(0.0, 1, a, 1), O.Settings(0, bounces, 1.0, 1.0, 0), spp)
     assert ref[..., :3].mean() > 0
@@ -36,7 +33,7 @@ def test_camref_default_camera_equals_oracle(name, w, h, spp, bounces):
 def test_camref_debug_views_equal_oracle(debug):
     rows = scenes.SCENES["c3"]().rows()
     w, h = 12, 8
-    a = _aspect(w, h)
+    a = G.aspect(w, h)
     got = camref.render(rows, w, h, 1, 1, a, 8, 1, debug=debug)
     ref = O.OracleScene(rows).render(w, h, O.Constants(0.0, 1, a, 1), O.Settings(debug, 8, 1.0, 1.0, 0), 1)
     assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
@@ -58,19 +55,19 @@ def test_look_at_reference_pose_is_identity():
 
 
 def test_look_at_basis_is_orthonormal():
-    cam = _look_at((2.0, 1.5, -2.5), (0, 0, 0), aperture=0.05, focus=3.0)
+    cam = G.camera("lens")
     r, u, f = (np.array(list(v), np.float64) for v in (cam.right, cam.up, cam.forward))
     for a in (r, u, f):
         assert abs(np.dot(a, a) - 1.0) < 1e-6
     assert abs(np.dot(r, u)) < 1e-6 and abs(np.dot(r, f)) < 1e-6 and abs(np.dot(u, f)) < 1e-6
     # oriented like the reference's view (x right, y up, z forward), and forward points at the target
     assert np.allclose(np.cross(r, u), f, atol=1e-6)
-    eye = np.array([2.0, 1.5, -2.5])
+    eye = np.array(G.EYE)
     assert np.allclose(f, -eye / np.linalg.norm(eye), atol=1e-6)
     assert list(cam.origin) == [2.0, 1.5, -2.5]
     assert cam.aperture == float(F(0.05)) and cam.focus == 3.0
     # focus defaults to the distance to the target, in float32
-    d = _look_at((2.0, 1.5, -2.5), (0, 0, 0)).focus
+    d = G.camera("pinhole").focus
     assert d == float(np.sqrt(F(2.0) * F(2.0) + F(1.5) * F(1.5) + F(2.5) * F(2.5)))
 
 
@@ -93,7 +90,6 @@ def test_test_camera_sees_the_scene(name, w, h, spp, pinhole, lens):
     recorded when the camera was chosen (a wrong basis or draw order moves
     these counts)."""
     rows = scenes.SCENES[name]().rows()
-    a = _aspect(w, h)
-    assert camref.primary_hits(rows, w, h, 1, a, spp, camera=_look_at((2.0, 1.5, -2.5), (0, 0, 0))) == pinhole
-    cam = _look_at((2.0, 1.5, -2.5), (0, 0, 0), aperture=0.05, focus=3.0)
-    assert camref.primary_hits(rows, w, h, 1, a, spp, camera=cam) == lens
+    a = G.aspect(w, h)
+    assert camref.primary_hits(rows, w, h, 1, a, spp, camera=G.camera("pinhole")) == pinhole
+    assert camref.primary_hits(rows, w, h, 1, a, spp, camera=G.camera("lens")) == lens

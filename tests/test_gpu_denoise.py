@@ -12,45 +12,34 @@ import numpy as np
 import pytest
 
 import denoiseref as D
+import gpuharness as G
 from compute_path_tracer_amd import _native as N
 from compute_path_tracer_amd import scenes
-from compute_path_tracer_amd.path_tracer import PathTracer, look_at_camera
 from compute_path_tracer_amd.sdf_editor import CompData
+from gpuharness import EYE, SKY, TARGET  # the camera tests' pose: part of the frame stays empty
+from gpuharness import bits as _bits
 from oracle import oracle as O
 from test_display import SPECIAL
 
 pytestmark = pytest.mark.gpu
 
 W, H = 61, 37
-EYE, TARGET = (2.0, 1.5, -2.5), (0.0, 0.0, 0.0)  # test_gpu_camera.py's pose: part of the frame stays empty
-SKY = dict(bottom=(0.9, 0.8, 0.7), top=(0.25, 0.45, 0.9), sun_direction=(0.4, 0.7, -0.6), sun_color=(8.0, 7.0, 5.0),
-           sun_angle=30.0)
 DEFAULTS = dict(iterations=5, sigma_color=2.0, sigma_depth=0.05, sigma_albedo=0.1, normal_power_log2=5)
 
 
-def _aspect(w, h):
-    return float(np.float32(w) / np.float32(h))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _tracer(name="c2", w=W, h=H, bounces=4, **options):
-    prog = scenes.SCENES[name]().compile(CompData())
-    return PathTracer(w, h, prog, settings=N.Settings(debug=0, bounces=bounces, scale=1.0, fov=1.0, aabb=0),
-                      options=options)
+    return G.tracer(name, w, h, bounces, extra=options)
 
 
 def _constants(w=W, h=H, frame=1):
-    return N.Constants(time=0.0, frame=frame, aspect=_aspect(w, h), last_clear=frame)
+    return G.constants(w, h, frame, frame)
 
 
 @functools.lru_cache(maxsize=None)
 def _guides_ref(posed):
     """denoiseref's guide images, computed once per view and shared (read-only)."""
-    cam = look_at_camera(EYE, TARGET) if posed else None
-    g0, g1 = D.guides(scenes.c2_sphere_box_torus().rows(), W, H, _aspect(W, H), 1.0, cam)
+    g0, g1 = D.guides(scenes.c2_sphere_box_torus().rows(), W, H, G.aspect(W, H), 1.0,
+                      G.camera("pinhole" if posed else "default"))
     g0.setflags(write=False)
     g1.setflags(write=False)
     return g0, g1

@@ -8,54 +8,23 @@ import time
 import numpy as np
 import pytest
 
+import camref
 import fuzzref as R
-import skyref
+import gpuharness as G
 from compute_path_tracer_amd import _native as N
 from compute_path_tracer_amd import scenes
-from compute_path_tracer_amd.path_tracer import PathTracer, look_at_camera, sky_light
 from compute_path_tracer_amd.sdf_editor import CompData
+from gpuharness import INTERPRETERS, KERNELS, SCENE_KERNELS
 
 pytestmark = pytest.mark.gpu
 
-# the option table of test_gpu_parity.py
-KERNELS = {"simple": {"kernel": "simple", "jit": 0}, "wave": {"kernel": "wave", "jit": 0},
-           "jit": {"kernel": "wave", "jit": 1, "jit_bake": 0}, "binned": {"kernel": "binned", "jit": 0},
-           "binned_jit": {"kernel": "binned", "jit": 1, "jit_bake": 0},
-           "binned_bake": {"kernel": "binned", "jit": 1, "jit_bake": 1},
-           "binned_tier": {"kernel": "binned", "jit": 1, "jit_bake": 2},
-           "binned_trace_taps": {"kernel": "binned", "jit": 1, "jit_bake": 2, "shade_taps": 0},
-           "binned_jit_trace_taps": {"kernel": "binned", "jit": 1, "jit_bake": 0, "shade_taps": 0}}
-INTERPRETERS = ["simple", "wave", "binned"]
-SCENE_KERNELS = ["jit", "binned_jit", "binned_bake", "binned_tier", "binned_trace_taps"]
 # test_work_counters_match_oracle's keys, and the torus the random scenes add
 COUNTERS = ("samples", "segments", "march_steps", "normal_maps", "shaded", "aabb_tests", "xform_union", "xform_shape",
             "sdf_sphere", "sdf_cube", "sdf_torus", "sdf_octahedron", "comb_union", "comb_sub", "comb_assign", "rr_break")
 
 
-def _constants(w, h):
-    return N.Constants(time=0.0, frame=1, aspect=R.aspect(w, h), last_clear=1)
-
-
-def _tracer(prog, w, h, bounces, kernel, extra=None):
-    opts = dict(KERNELS[kernel])
-    opts.update(extra or {})
-    pt = PathTracer(w, h, prog, settings=N.Settings(debug=0, bounces=bounces, scale=1.0, fov=1.0, aabb=0), options=opts)
-    if prog is not None:
-        _ready(pt, opts)
-    return pt
-
-
-def _ready(pt, opts):
-    """No quiet fall-back: the scene kernel serves, and jit_bake 2 runs on its values-baked build."""
-    if opts["jit"]:
-        assert pt.get_option("jit_active") == 1.0, pt.jit_log()
-    if opts.get("jit_bake") == 2:
-        pt.set_option("jit_wait", 1)
-        assert pt.get_option("jit_tier_active") == 1.0, pt.jit_log()
-
-
 def _image(pt, w, h, spp):
-    pt.dispatch(_constants(w, h), spp)
+    pt.dispatch(G.constants(w, h), spp)
     return pt.read_image()
 
 
@@ -65,12 +34,12 @@ def test_corpus_on_interpreter_kernels(gpu, kernel):
     the work counters of the same context against the oracle's."""
     for k, seed in enumerate(scenes.FUZZ_SEEDS):
         ed = scenes.fuzz_scene(seed)
-        pt = _tracer(ed.compile(CompData()), R.W, R.H, R.BOUNCES, kernel)
+        pt = G.tracer(ed.compile(CompData()), R.W, R.H, R.BOUNCES, kernel)
         img = _image(pt, R.W, R.H, R.SPP)
         diff = R.first_difference(img, R.fuzz_oracle(seed))
         assert diff is None, f"seed {seed} on {kernel}: {diff}"
         if k % 4 == 0:
-            got = pt.stats(_constants(R.W, R.H), R.SPP)
+            got = pt.stats(G.constants(R.W, R.H), R.SPP)
             _, want = R.oracle_image(ed, R.W, R.H, R.SPP, R.BOUNCES, counters=True)
             bad = {c: (got[c], want[c]) for c in COUNTERS if got[c] != want[c]}
             assert not bad, f"seed {seed} on {kernel}: counters (got, oracle) {bad}"
@@ -87,7 +56,7 @@ def test_small_scenes_on_scene_kernels(gpu, seed, profile, kernel):
     for bounces in (R.BOUNCES, 0) if profile == "deep" else (R.BOUNCES,):
         want = R.fuzz_oracle(seed, profile, R.W, R.H, R.SPP, bounces)
         for lanes in (1, 2) if kernel.startswith("binned") else (None,):
-            pt = _tracer(prog, R.W, R.H, bounces, kernel, extra={"bin_lanes": lanes} if lanes else None)
+            pt = G.tracer(prog, R.W, R.H, bounces, kernel, extra={"bin_lanes": lanes} if lanes else None)
             diff = R.first_difference(_image(pt, R.W, R.H, R.SPP), want)
             pt.close()
             assert diff is None, f"fuzz-{seed} on {kernel}, bin_lanes {lanes}, {bounces} bounces: {diff}"
@@ -106,30 +75,27 @@ def test_nan_in_a_transform(gpu, name, kernel):
     ed = scenes.SCENES[name]()
     want = R.oracle_image(ed, R.W, R.H, R.SPP, R.BOUNCES)
     assert want[..., :3].mean() > 0
-    pt = _tracer(ed.compile(CompData()), R.W, R.H, R.BOUNCES, kernel)
+    pt = G.tracer(ed.compile(CompData()), R.W, R.H, R.BOUNCES, kernel)
     diff = R.first_difference(_image(pt, R.W, R.H, R.SPP), want)
     pt.close()
     assert diff is None, f"{name} on {kernel}: {diff}"
 
 
-# test_gpu_sky.py's lens camera and sky
-EYE, TARGET, LENS = (2.0, 1.5, -2.5), (0.0, 0.0, 0.0), {"aperture": 0.05, "focus": 3.0}
-SKY = dict(bottom=(0.9, 0.8, 0.7), top=(0.25, 0.45, 0.9), sun_direction=(0.4, 0.7, -0.6), sun_color=(8.0, 7.0, 5.0),
-           sun_angle=30.0)
 _sky_refs = {}
 
 
 @pytest.mark.parametrize("kernel", ["binned", "binned_tier"])
 @pytest.mark.parametrize("seed", [154, 15793])
 def test_posed_camera_and_sky(gpu, seed, kernel):
+    """The camera and sky tests' lens camera and sky."""
     w, h, spp, bounces = 12, 8, 1, 3
     ed = scenes.SCENES[f"fuzz-{seed}"]()
     if seed not in _sky_refs:
-        _sky_refs[seed] = skyref.render(ed.rows(), w, h, 1, 1, R.aspect(w, h), bounces, spp,
-                                        camera=look_at_camera(EYE, TARGET, **LENS), sky=sky_light(**SKY))
-    pt = _tracer(ed.compile(CompData()), w, h, bounces, kernel)
-    pt.look_at(EYE, TARGET, **LENS)
-    pt.set_sky(**SKY)
+        _sky_refs[seed] = camref.render(ed.rows(), w, h, 1, 1, G.aspect(w, h), bounces, spp, camera=G.camera("lens"),
+                                        sky=G.sky())
+    pt = G.tracer(ed.compile(CompData()), w, h, bounces, kernel)
+    pt.look_at(G.EYE, G.TARGET, **G.LOOK["lens"])
+    pt.set_sky(**G.SKY)
     diff = R.first_difference(_image(pt, w, h, spp), _sky_refs[seed])
     pt.close()
     assert diff is None, f"fuzz-{seed} on {kernel}: {diff}"
@@ -138,7 +104,7 @@ def test_posed_camera_and_sky(gpu, seed, kernel):
 def _refused_then_serves(kernel, bad, good, w, h, spp, bounces):
     """pt_set_program refuses `bad` on the host (PT_ERR_UNSUPPORTED, nothing
     launched); the same context then takes `good` and renders it exactly."""
-    pt = _tracer(None, w, h, bounces, kernel)
+    pt = G.tracer(None, w, h, bounces, kernel)
     with pytest.raises(N.NativeError) as e:
         pt.remake_pipeline(bad.compile(CompData()))
     assert e.value.code == N.PT_ERR_UNSUPPORTED
@@ -159,7 +125,7 @@ def test_check_limit(gpu, kernel):
     assert prog.n_check == prog.n_aabb == 128
     want = R.oracle_image(full, w, h, spp, bounces)
     assert want[..., :3].mean() > 0
-    pt = _tracer(prog, w, h, bounces, kernel)
+    pt = G.tracer(prog, w, h, bounces, kernel)
     diff = R.first_difference(_image(pt, w, h, spp), want)
     pt.close()
     assert diff is None, diff
@@ -174,7 +140,7 @@ def test_depth_limit(gpu, kernel):
     seed, profile = scenes.FUZZ_JIT_SEEDS[-1]
     assert profile == "deep"
     deep = scenes.fuzz_scene(seed, profile)
-    pt = _tracer(deep.compile(CompData()), R.W, R.H, R.BOUNCES, kernel)
+    pt = G.tracer(deep.compile(CompData()), R.W, R.H, R.BOUNCES, kernel)
     diff = R.first_difference(_image(pt, R.W, R.H, R.SPP), R.fuzz_oracle(seed, profile))
     pt.close()
     assert diff is None, diff
@@ -207,7 +173,7 @@ def test_live_edits_on_one_context(gpu, kernel):
     opts = KERNELS[kernel]
     ed = scenes.c3_graph32()
     cd = CompData()
-    pt = _tracer(ed.compile(cd), w, h, bounces, kernel)
+    pt = G.tracer(ed.compile(cd), w, h, bounces, kernel)
     images = [R.oracle_image(ed, w, h, spp, bounces)]
     diff = R.first_difference(_image(pt, w, h, spp), images[0])
     assert diff is None, f"before any edit: {diff}"
@@ -219,7 +185,7 @@ def test_live_edits_on_one_context(gpu, kernel):
         pt.set_data(cd.data_array.as_array())
         took = time.perf_counter() - t0
         pt.clear()
-        _ready(pt, opts)
+        G.ready(pt, opts)
         assert _derived(pt) == state, label  # the thresholds the step is named for
         if changes_source and opts["jit"]:
             print(f"{kernel}: '{label}' changed the source: set_data took {took:.1f} s "
@@ -232,7 +198,7 @@ def test_live_edits_on_one_context(gpu, kernel):
         diff = R.first_difference(_image(pt, w, h, spp), images[-1])
         assert diff is None, f"{kernel} after '{label}': {diff}"
     # what the context derived from the data, against a fresh context given the final data
-    fresh = _tracer(ed.compile(CompData()), w, h, bounces, kernel)
+    fresh = G.tracer(ed.compile(CompData()), w, h, bounces, kernel)
     assert pt.get_option("jit_active") == fresh.get_option("jit_active") == float(opts["jit"])
     assert _derived(pt) == _derived(fresh) and pt.get_option("bound_k") == fresh.get_option("bound_k")
     diff = R.first_difference(_image(fresh, w, h, spp), images[-1])

@@ -12,10 +12,12 @@ import functools
 import numpy as np
 import pytest
 
+import gpuharness as G
 import meshref as M
 from compute_path_tracer_amd import _native as N
 from compute_path_tracer_amd import scenes
-from compute_path_tracer_amd.path_tracer import Mesh, PathTracer, mesh_grid
+from compute_path_tracer_amd.path_tracer import Mesh, mesh_grid
+from gpuharness import EYE, TARGET
 from compute_path_tracer_amd.sdf_editor import CompData, SDFEditor
 from oracle import oracle as O
 
@@ -41,20 +43,19 @@ def reference(name, grid, iso, project):
     return M.extract(oracle_scene(name), *grid, iso, project)
 
 
+def _tracer_of(ed, **options):
+    """A 16 x 16 context on the interpreter kernels unless `options` say otherwise."""
+    return G.tracer(ed, 16, 16, 2, extra=dict({"jit": 0}, **options))
+
+
 def tracer(name, **options):
     ed = editor(name)
-    opts = {"jit": 0}
-    opts.update(options)
-    pt = PathTracer(16, 16, ed.compile(CompData()), settings=N.Settings(debug=0, bounces=2, scale=1.0, fov=1.0, aabb=0),
-                    options=opts)
-    if opts["jit"]:
-        assert pt.get_option("jit_active") == 1.0, pt.jit_log()
-    return pt, ed
+    return _tracer_of(ed, **options), ed
 
 
 def same_bits(a, b):
     a, b = np.asarray(a, F), np.asarray(b, F)
-    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+    return a.shape == b.shape and bool(G.same_or_nan(a, b).all())
 
 
 def assert_matches(mesh: Mesh, ref, rows, prog, data=None, what=""):
@@ -167,11 +168,6 @@ def sphere_scene(radius, scale=1.0):
     return ed
 
 
-def _tracer_of(ed):
-    return PathTracer(16, 16, ed.compile(CompData()), settings=N.Settings(debug=0, bounces=2, scale=1.0, fov=1.0, aabb=0),
-                      options={"jit": 0})
-
-
 def test_the_skip_really_skips(gpu):
     """A sphere of radius 0.5 in [-2, 2]^3 at cell 1/16: 512 bricks of side 0.5
     and half-diagonal 0.433.  Only the 8 bricks around the origin and the 24
@@ -236,7 +232,7 @@ def test_value_edits_and_snapshots(gpu):
     ed = scenes.SCENES["c2"]()
     cd = CompData()
     prog = ed.compile(cd)
-    pt = PathTracer(16, 16, prog, settings=N.Settings(debug=0, bounces=2, scale=1.0, fov=1.0, aabb=0), options={"jit": 0})
+    pt = _tracer_of(prog)
     grid = GRIDS["c2"]
     first = pt.extract_mesh(grid=grid, project=2)
     sphere = ed.header_unions[0].children_shapes[1]
@@ -257,8 +253,8 @@ def test_value_edits_and_snapshots(gpu):
 def test_no_side_effects(gpu):
     """The image, the guides' validity, the camera, the sky and the options stay as they were."""
     pt, _ = tracer("c2", kernel="binned")
-    k = N.Constants(time=0.0, frame=1, aspect=1.0, last_clear=1)
-    pt.look_at((2.0, 1.5, -2.5), (0.0, 0.0, 0.0))
+    k = G.constants(16, 16)
+    pt.look_at(EYE, TARGET)
     pt.set_sky((0.9, 0.8, 0.7), (0.2, 0.4, 0.9))
     pt.dispatch(k, 2)
     before = pt.read_image()
@@ -282,7 +278,7 @@ def test_no_side_effects(gpu):
 
 def test_argument_and_state_errors(gpu):
     L = N.lib()
-    pt = PathTracer(16, 16, None, options={"jit": 0})
+    pt = _tracer_of(None)
     desc = N.MeshDesc(cell=0.25, iso=0.0, project=1)
     for k in range(3):
         desc.origin[k], desc.cells[k] = -2.0, 16

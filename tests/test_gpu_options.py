@@ -7,13 +7,10 @@ leaves behind.  An 8 x 8 context, scene c1, 4 bounces.
 import ctypes
 import math
 
-import numpy as np
 import pytest
 
+import gpuharness as G
 from compute_path_tracer_amd import _native as N
-from compute_path_tracer_amd import scenes
-from compute_path_tracer_amd.path_tracer import PathTracer
-from compute_path_tracer_amd.sdf_editor import CompData
 
 pytestmark = pytest.mark.gpu
 
@@ -45,9 +42,7 @@ BYTES_PER_SAMPLE = 2 * 64 + 16 + 8 + 16
 
 
 def _tracer(options=None):
-    prog = scenes.SCENES["c1"]().compile(CompData())
-    return PathTracer(W, H, prog, settings=N.Settings(debug=0, bounces=BOUNCES, scale=1.0, fov=1.0, aabb=0),
-                      options=options)
+    return G.tracer("c1", W, H, BOUNCES, extra=options)
 
 
 def _set(pt, key, value):
@@ -85,7 +80,7 @@ def dispatched():
 
 
 def _constants():
-    return N.Constants(time=0.0, frame=1, aspect=1.0, last_clear=1)
+    return G.constants(W, H)
 
 
 def test_fresh_context_readings():
@@ -187,5 +182,5 @@ def test_jit_off_unloads_and_stays_bit_exact(dispatched):
     pt.clear()
     pt.dispatch(_constants(), SPP)
     after = pt.read_image()
-    assert np.array_equal(after.view(np.uint32), before.view(np.uint32))
+    assert G.same_bits(after, before) == 1.0
     assert pt.get_option("trace_launches") == LANES * (BOUNCES + 1)

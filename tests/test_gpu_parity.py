@@ -10,10 +10,12 @@ import ctypes
 import numpy as np
 import pytest
 
+import gpuharness as G
 from compute_path_tracer_amd import _native as N
 from compute_path_tracer_amd import scenes
 from compute_path_tracer_amd.path_tracer import PathTracer
 from compute_path_tracer_amd.sdf_editor import CompData
+from gpuharness import ALL, KERNELS
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -21,46 +23,21 @@ pytestmark = pytest.mark.gpu
 RMS_TOL = 1e-5
 
 
-KERNELS = {"simple": {"kernel": "simple", "jit": 0}, "wave": {"kernel": "wave", "jit": 0},
-           "jit": {"kernel": "wave", "jit": 1, "jit_bake": 0}, "binned": {"kernel": "binned", "jit": 0},
-           "binned_jit": {"kernel": "binned", "jit": 1, "jit_bake": 0},
-           "binned_bake": {"kernel": "binned", "jit": 1, "jit_bake": 1},
-           "binned_tier": {"kernel": "binned", "jit": 1, "jit_bake": 2},
-           # normal taps in the trace pass instead of the shade pass
-           "binned_trace_taps": {"kernel": "binned", "jit": 1, "jit_bake": 2, "shade_taps": 0}}
-ALL = ["simple", "wave", "jit", "binned", "binned_jit", "binned_bake", "binned_tier", "binned_trace_taps"]
-
-
-def _tier_up(pt, opts):
-    """jit_bake 2: wait for the values-baked build, so the test runs on it."""
-    if opts.get("jit_bake") == 2:
-        pt.set_option("jit_wait", 1)
-        assert pt.get_option("jit_tier_active") == 1.0, pt.jit_log()
-
-
-def _render_pair(ed, w, h, spp, bounces, debug=0, frame=1, last_clear=1, fov=1.0, aspect=None, kernel="jit",
-                 shade_batch=None, bin_samples=None, bin_lanes=None, extra=None):
-    prog = ed.compile(CompData())
-    st = N.Settings(debug=debug, bounces=bounces, scale=1.0, fov=fov, aabb=0)
-    opts = dict(KERNELS[kernel])
-    opts.update(extra or {})
+def _render_pair(scene, w, h, spp, bounces, debug=0, fov=1.0, kernel="jit", shade_batch=None, bin_samples=None,
+                 bin_lanes=None, extra=None):
+    """The GPU image and the oracle's, of a SCENES name or an editor."""
+    opts = dict(extra or {})
     if shade_batch:
         opts["shade_batch"] = shade_batch
     if bin_samples:
         opts["bin_samples"] = bin_samples
     if bin_lanes:
         opts["bin_lanes"] = bin_lanes
-    pt = PathTracer(w, h, prog, settings=st, options=opts)
-    if opts["jit"]:
-        assert pt.get_option("jit_active") == 1.0, pt.jit_log()
-    _tier_up(pt, opts)
-    a = float(np.float32(w) / np.float32(h)) if aspect is None else aspect
-    pt.dispatch(N.Constants(time=0.0, frame=frame, aspect=a, last_clear=last_clear), spp)
+    pt = G.tracer(scene, w, h, bounces, kernel, debug, opts, fov=fov)
+    pt.dispatch(G.constants(w, h), spp)
     gpu = pt.read_image()
     pt.close()
-    ref = O.OracleScene(ed.rows()).render(w, h, O.Constants(0.0, frame, a, last_clear),
-                                          O.Settings(debug, bounces, 1.0, fov, 0), spp)
-    return gpu, ref
+    return gpu, G.oracle_image(scene, w, h, spp, bounces, debug, fov=fov)
 
 
 def _report(gpu, ref):
@@ -85,7 +62,7 @@ def _report(gpu, ref):
     ("farbox", 64, 40, 3, 4),      # a box coordinate beyond the reciprocal guard: IEEE-division bounds()
 ])
 def test_parity_path_trace(gpu, name, w, h, spp, bounces, kernel):
-    gpu_img, ref = _render_pair(scenes.SCENES[name](), w, h, spp, bounces, kernel=kernel)
+    gpu_img, ref = _render_pair(name, w, h, spp, bounces, kernel=kernel)
     rms, exact = _report(gpu_img, ref)
     print(f"{kernel} {name}: rms={rms:.3e} bit-exact={exact:.5f} mean={ref[..., :3].mean():.5f}")
     assert ref[..., :3].mean() > 0
@@ -96,7 +73,7 @@ def test_parity_path_trace(gpu, name, w, h, spp, bounces, kernel):
 @pytest.mark.parametrize("kernel", ALL)
 @pytest.mark.parametrize("debug", [1, 2, 3])
 def test_parity_debug_views(gpu, debug, kernel):
-    gpu_img, ref = _render_pair(scenes.c3_graph32(), 80, 45, 2, 8, debug=debug, kernel=kernel)
+    gpu_img, ref = _render_pair("c3", 80, 45, 2, 8, debug=debug, kernel=kernel)
     rms, exact = _report(gpu_img, ref)
     assert rms < RMS_TOL and exact == 1.0
 
@@ -106,7 +83,7 @@ def test_parity_debug_views(gpu, debug, kernel):
 def test_wave_kernel_schedule_invariance(gpu, shade_batch, kernel):
     """Shading batch size changes the schedule only, never the result; spp
     above the LDS ring size exercises the in-order fold."""
-    gpu_img, ref = _render_pair(scenes.c3_graph32(), 40, 24, 19, 8, kernel=kernel, shade_batch=shade_batch)
+    gpu_img, ref = _render_pair("c3", 40, 24, 19, 8, kernel=kernel, shade_batch=shade_batch)
     rms, exact = _report(gpu_img, ref)
     assert exact == 1.0, (shade_batch, rms)
 
@@ -120,7 +97,7 @@ def test_first_pass_box_skip_edges(gpu, kernel, fov):
     wide field of view (fov is rd.z before normalising: at 0.02 a window's
     rays are nearly parallel to the image plane's axes, at 5 nearly along
     z).  Bit-exact against the oracle on C3's 24 boxes."""
-    gpu_img, ref = _render_pair(scenes.c3_graph32(), 72, 40, 2, 3, fov=fov, kernel=kernel)
+    gpu_img, ref = _render_pair("c3", 72, 40, 2, 3, fov=fov, kernel=kernel)
     rms, exact = _report(gpu_img, ref)
     assert exact == 1.0 and rms == 0.0, (rms, exact)
 
@@ -128,7 +105,7 @@ def test_first_pass_box_skip_edges(gpu, kernel, fov):
 @pytest.mark.parametrize("kernel", ["jit", "binned_jit"])
 def test_long_dispatch_chunks(gpu, kernel):
     """spp > 64 is split into several launches that continue frame/last_clear."""
-    gpu_img, ref = _render_pair(scenes.c1_default(), 16, 16, 70, 1, kernel=kernel)
+    gpu_img, ref = _render_pair("c1", 16, 16, 70, 1, kernel=kernel)
     rms, exact = _report(gpu_img, ref)
     assert exact == 1.0
 
@@ -138,7 +115,7 @@ def test_binned_sub_chunks(gpu, bin_samples):
     """The binned pipeline splits a dispatch into sub-chunks of frames that fit
     its sample budget (one frame when the budget is below the pixel count);
     the fold continues last_clear across them."""
-    gpu_img, ref = _render_pair(scenes.c3_graph32(), 40, 24, 11, 8, kernel="binned_jit", bin_samples=bin_samples)
+    gpu_img, ref = _render_pair("c3", 40, 24, 11, 8, kernel="binned_jit", bin_samples=bin_samples)
     rms, exact = _report(gpu_img, ref)
     assert exact == 1.0, rms
 
@@ -148,7 +125,7 @@ def test_binned_sub_chunks(gpu, bin_samples):
 def test_binned_lanes(gpu, bin_lanes, spp, bin_samples):
     """A chunk's frames split over one to four pipelines on separate streams
     (ragged splits, one-frame chunks, several chunks) fold to the same image."""
-    gpu_img, ref = _render_pair(scenes.c3_graph32(), 40, 24, spp, 8, kernel="binned_tier", bin_samples=bin_samples,
+    gpu_img, ref = _render_pair("c3", 40, 24, spp, 8, kernel="binned_tier", bin_samples=bin_samples,
                                 bin_lanes=bin_lanes)
     rms, exact = _report(gpu_img, ref)
     assert exact == 1.0, rms
@@ -162,7 +139,7 @@ def test_bin_table_schedule_only(gpu, kernel, bin_table, name, spp, bin_lanes):
     3.21) or from the hash: the schedule changes, the image does not.  C3
     (24 boxes) and `cull` use the table, with one to three pipelines sharing
     it; C3 without boxes has one set."""
-    gpu_img, ref = _render_pair(scenes.SCENES[name](), 96, 54, spp, 8, kernel=kernel, bin_lanes=bin_lanes,
+    gpu_img, ref = _render_pair(name, 96, 54, spp, 8, kernel=kernel, bin_lanes=bin_lanes,
                                 extra={"bin_table": bin_table})
     rms, exact = _report(gpu_img, ref)
     assert exact == 1.0 and rms == 0.0, (rms, exact)
@@ -175,25 +152,19 @@ def test_first_pass_without_records(gpu, kernel, bin_lanes):
     C3's 24 check[] entries, so it stores no ray records and shade pass 0
     makes them again, with one and two pipelines:
     bit-exact against the oracle."""
-    ed = scenes.c3_graph32()
-    prog = ed.compile(CompData())
     w, h, spp = 64, 48, 6
-    opts = dict(KERNELS[kernel], bin_lanes=bin_lanes)
-    pt = PathTracer(w, h, prog, settings=N.Settings(debug=0, bounces=8, scale=1.0, fov=1.0, aabb=0), options=opts)
-    _tier_up(pt, opts)
-    a = float(np.float32(w) / np.float32(h))
-    pt.dispatch(N.Constants(time=0.0, frame=1, aspect=a, last_clear=1), spp)
+    pt = G.tracer("c3", w, h, 8, kernel, extra={"bin_lanes": bin_lanes})
+    pt.dispatch(G.constants(w, h), spp)
     gpu_img = pt.read_image()
     assert pt.get_option("gen_trace") == 1.0 and pt.get_option("gen_norec") == 1.0
     pt.close()
-    ref = O.OracleScene(ed.rows()).render(w, h, O.Constants(0.0, 1, a, 1), O.Settings(0, 8, 1.0, 1.0, 0), spp)
-    rms, exact = _report(gpu_img, ref)
+    rms, exact = _report(gpu_img, G.oracle_image("c3", w, h, spp, 8))
     assert exact == 1.0 and rms == 0.0, (rms, exact)
 
 
 @pytest.mark.parametrize("kernel", ["jit", "binned_jit"])
 def test_empty_scene_is_black(gpu, kernel):
-    gpu_img, ref = _render_pair(scenes.empty(), 40, 24, 2, 4, kernel=kernel)
+    gpu_img, ref = _render_pair("empty", 40, 24, 2, 4, kernel=kernel)
     assert np.all(gpu_img[..., :3] == 0) and np.all(gpu_img[..., 3] == 1)
     assert np.array_equal(gpu_img, ref)
 
@@ -201,18 +172,16 @@ def test_empty_scene_is_black(gpu, kernel):
 @pytest.mark.parametrize("kernel", ["jit", "binned_jit"])
 def test_ragged_and_edge_sizes(gpu, kernel):
     for (w, h) in [(1, 1), (7, 3), (9, 17), (65, 1)]:
-        gpu_img, ref = _render_pair(scenes.c2_sphere_box_torus(), w, h, 2, 3, kernel=kernel)
+        gpu_img, ref = _render_pair("c2", w, h, 2, 3, kernel=kernel)
         rms, exact = _report(gpu_img, ref)
         assert exact == 1.0, (w, h)
 
 
 def test_progressive_equals_batched(gpu):
     """spp successive 1-spp frames == one spp dispatch (path_tracer.rs:110-111)."""
-    ed = scenes.c2_sphere_box_torus()
-    prog = ed.compile(CompData())
-    st = N.Settings(debug=0, bounces=4, scale=1.0, fov=1.0, aabb=0)
-    a = PathTracer(48, 32, prog, settings=st)
-    b = PathTracer(48, 32, prog, settings=st)
+    prog = scenes.c2_sphere_box_torus().compile(CompData())
+    a = G.tracer(prog, 48, 32, 4)
+    b = G.tracer(prog, 48, 32, 4)
     for _ in range(5):
         a.update()
         a.compute_pass()
@@ -221,8 +190,7 @@ def test_progressive_equals_batched(gpu):
     b.constants.last_clear -= 1
     b.render(5)
     ia, ib = a.read_image(), b.read_image()
-    ref = O.OracleScene(ed.rows()).render(48, 32, O.Constants(0.0, 1, float(np.float32(48) / np.float32(32)), 1),
-                                          O.Settings(0, 4, 1.0, 1.0, 0), 5)
+    ref = G.oracle_image("c2", 48, 32, 5, 4)
     bad_a = (ia.view(np.uint32) != ref.view(np.uint32)).any(-1)
     bad_b = (ib.view(np.uint32) != ref.view(np.uint32)).any(-1)
     assert not bad_a.any() and not bad_b.any(), (np.argwhere(bad_a)[:8].tolist(), np.argwhere(bad_b)[:8].tolist())
@@ -231,16 +199,14 @@ def test_progressive_equals_batched(gpu):
 
 @pytest.mark.parametrize("kernel", ["jit", "binned_jit"])
 def test_tiles_union_is_full_image(gpu, kernel):
-    ed = scenes.c3_graph32()
-    prog = ed.compile(CompData())
-    st = N.Settings(debug=0, bounces=8, scale=1.0, fov=1.0, aabb=0)
-    c = N.Constants(time=0.0, frame=3, aspect=float(np.float32(72) / np.float32(40)), last_clear=1)
-    full = PathTracer(72, 40, prog, settings=st)
+    prog = scenes.c3_graph32().compile(CompData())
+    c = G.constants(72, 40, frame=3)
+    full = G.tracer(prog, 72, 40, 8)
     full.dispatch(c, 2)
     ref = full.read_image()
     acc = np.zeros_like(ref)
     for r in range(3):
-        p = PathTracer(72, 40, prog, settings=st, options=KERNELS[kernel])
+        p = G.tracer(prog, 72, 40, 8, kernel)
         p.set_tiles(r, 3)
         p.dispatch(c, 2)
         acc += p.read_image()
@@ -253,10 +219,7 @@ def test_jit_recompiles_only_on_flag_change(gpu):
     non-zero) rebuilds it; results stay exact throughout."""
     ed = scenes.c2_sphere_box_torus()
     cd = CompData()
-    prog = ed.compile(cd)
-    st = N.Settings(debug=0, bounces=3, scale=1.0, fov=1.0, aabb=0)
-    pt = PathTracer(40, 30, prog, settings=st, options={"jit": 1})
-    assert pt.get_option("jit_active") == 1.0
+    pt = G.tracer(ed.compile(cd), 40, 30, 3, extra={"jit": 1})
     sph = ed.header_unions[0].children_shapes[1]
     sph.transform.position.x.set(-0.3)  # value only
     ed.data_update(cd)
@@ -266,41 +229,27 @@ def test_jit_recompiles_only_on_flag_change(gpu):
     ed.data_update(cd)
     pt.set_data(cd.data_array.as_array())
     assert pt.get_option("jit_active") == 1.0
-    c = N.Constants(time=0.0, frame=1, aspect=float(np.float32(40) / np.float32(30)), last_clear=1)
-    pt.dispatch(c, 2)
-    gpu_img = pt.read_image()
-    ref = O.OracleScene(ed.rows()).render(40, 30, O.Constants(0.0, 1, c.aspect, 1), O.Settings(0, 3, 1.0, 1.0, 0), 2)
-    assert np.array_equal(gpu_img.view(np.uint32), ref.view(np.uint32))
+    pt.dispatch(G.constants(40, 30), 2)
+    assert G.same_bits(pt.read_image(), G.oracle_image(ed, 40, 30, 2, 3)) == 1.0
 
 
 def test_value_update_without_recompile(gpu):
     ed = scenes.c2_sphere_box_torus()
     cd = CompData()
-    prog = ed.compile(cd)
-    st = N.Settings(debug=0, bounces=3, scale=1.0, fov=1.0, aabb=0)
-    pt = PathTracer(40, 30, prog, settings=st)
+    pt = G.tracer(ed.compile(cd), 40, 30, 3)
     sph = ed.header_unions[0].children_shapes[1]
     sph.transform.position.x.set(-0.3)
     ed.data_update(cd)
     pt.set_data(cd.data_array.as_array())
-    c = N.Constants(time=0.0, frame=1, aspect=float(np.float32(40) / np.float32(30)), last_clear=1)
-    pt.dispatch(c, 2)
-    gpu_img = pt.read_image()
-    ref = O.OracleScene(ed.rows()).render(40, 30, O.Constants(0.0, 1, c.aspect, 1), O.Settings(0, 3, 1.0, 1.0, 0), 2)
-    assert np.array_equal(gpu_img.view(np.uint32), ref.view(np.uint32))
+    pt.dispatch(G.constants(40, 30), 2)
+    assert G.same_bits(pt.read_image(), G.oracle_image(ed, 40, 30, 2, 3)) == 1.0
 
 
 @pytest.mark.parametrize("kernel", ALL)
 def test_work_counters_match_oracle(gpu, kernel):
-    ed = scenes.c3_graph32()
-    prog = ed.compile(CompData())
-    st = N.Settings(debug=0, bounces=8, scale=1.0, fov=1.0, aabb=0)
-    pt = PathTracer(64, 40, prog, settings=st, options=KERNELS[kernel])
-    _tier_up(pt, KERNELS[kernel])
-    a = float(np.float32(64) / np.float32(40))
-    got = pt.stats(N.Constants(time=0.0, frame=1, aspect=a, last_clear=1), 2)
-    _, ct = O.OracleScene(ed.rows()).render(64, 40, O.Constants(0.0, 1, a, 1), O.Settings(0, 8, 1.0, 1.0, 0), 2,
-                                            counters=True)
+    pt = G.tracer("c3", 64, 40, 8, kernel)
+    got = pt.stats(G.constants(64, 40), 2)
+    _, ct = G.oracle_image("c3", 64, 40, 2, 8, counters=True)
     for k in ("samples", "segments", "march_steps", "normal_maps", "shaded", "aabb_tests", "xform_union",
               "xform_shape", "sdf_sphere", "sdf_cube", "sdf_octahedron", "comb_union", "comb_sub", "comb_assign",
               "rr_break"):
@@ -323,12 +272,11 @@ def _oracle_tiles(ed, w, h, spp, bounces, tiles):
     from concurrent.futures import ThreadPoolExecutor
 
     tx, ntiles = (w + 7) // 8, ((w + 7) // 8) * ((h + 7) // 8)
-    aspect = float(np.float32(w) / np.float32(h))
     osc = O.OracleScene(ed.rows())
 
     def one(t):
-        ref = osc.render(w, h, O.Constants(0.0, 1, aspect, 1), O.Settings(0, bounces, 1.0, 1.0, 0), spp, rank=t,
-                         nranks=ntiles, threads=1)
+        ref = osc.render(w, h, O.Constants(0.0, 1, G.aspect(w, h), 1), O.Settings(0, bounces, 1.0, 1.0, 0), spp,
+                         rank=t, nranks=ntiles, threads=1)
         y0, x0 = (t // tx) * 8, (t % tx) * 8
         return ref[y0:y0 + 8, x0:x0 + 8].copy()
 
@@ -349,11 +297,9 @@ def test_full_size_tiles_match_oracle(gpu, name):
     upstream; at most 16), against the oracle rendering just that tile."""
     scene, w, h, spp, bounces = scenes.CONFIGS[name]
     ed = scenes.SCENES[scene]()
-    st = N.Settings(debug=0, bounces=bounces, scale=1.0, fov=1.0, aabb=0)
-    pt = PathTracer(w, h, ed.compile(CompData()), settings=st)
+    pt = G.tracer(ed, w, h, bounces)
     pt.set_option("jit_wait", 1)
-    aspect = float(np.float32(w) / np.float32(h))
-    pt.dispatch(N.Constants(time=0.0, frame=1, aspect=aspect, last_clear=1), spp)
+    pt.dispatch(G.constants(w, h), spp)
     img = pt.read_image()
     chunk = pt.get_option("bin_samples")
     pt.close()
@@ -375,7 +321,7 @@ def test_parity_bounce_range(gpu, bounces, kernel):
     """The Settings slider range (path_tracer.rs:160, 0..=32): segments
     i = 0..=bounces (test_compute.glsl:99), so 1, 17 and 33 passes of the
     binned pipeline, deep Russian roulette and ping-pong buffers."""
-    gpu_img, ref = _render_pair(scenes.c3_graph32(), 48, 32, 3, bounces, kernel=kernel)
+    gpu_img, ref = _render_pair("c3", 48, 32, 3, bounces, kernel=kernel)
     rms, exact = _report(gpu_img, ref)
     assert ref[..., :3].mean() > 0
     assert rms < RMS_TOL and exact == 1.0, (rms, exact)
@@ -387,7 +333,7 @@ def test_bounce_heat_map_edges(gpu, bounces, kernel):
     """debug 3 stores i / bounces (test_compute.glsl:163): at bounces 0 that
     is 0 / 0 = NaN for a miss and 1 / 0 = +inf for a hit; bit patterns must
     match the oracle, NaNs included."""
-    gpu_img, ref = _render_pair(scenes.c3_graph32(), 40, 24, 2, bounces, debug=3, kernel=kernel)
+    gpu_img, ref = _render_pair("c3", 40, 24, 2, bounces, debug=3, kernel=kernel)
     assert np.array_equal(gpu_img.view(np.uint32), ref.view(np.uint32))
     if bounces == 0:
         assert np.isnan(ref[..., 0]).any() and np.isinf(ref[..., 0]).any()
@@ -400,19 +346,17 @@ def test_tile_split_2160p_eight_ranks(gpu):
     on the host equal the one-context render bit for bit (non-owned texels
     are exactly 0)."""
     scene, w, h, _, bounces = scenes.CONFIGS["c4"]
-    ed = scenes.SCENES[scene]()
-    prog = ed.compile(CompData())
-    st = N.Settings(debug=0, bounces=bounces, scale=1.0, fov=1.0, aabb=0)
-    c = N.Constants(time=0.0, frame=1, aspect=float(np.float32(w) / np.float32(h)), last_clear=1)
+    prog = scenes.SCENES[scene]().compile(CompData())
+    c = G.constants(w, h)
     spp = 16
-    full = PathTracer(w, h, prog, settings=st)
+    full = G.tracer(prog, w, h, bounces)
     full.dispatch(c, spp)
     want = full.read_image()
     full.close()
     acc = np.zeros_like(want)
     owned = np.zeros(want.shape[:2], np.int32)
     for r in range(8):
-        p = PathTracer(w, h, prog, settings=st)
+        p = G.tracer(prog, w, h, bounces)
         p.set_tiles(r, 8)
         p.dispatch(c, spp)
         part = p.read_image()
@@ -429,10 +373,8 @@ def test_rccl_single_rank_reduce_and_errors(gpu):
     GPU (a 1-rank communicator: the reduce is a copy), plus their argument
     and state errors."""
     L = N.lib()
-    ed = scenes.c2_sphere_box_torus()
-    st = N.Settings(debug=0, bounces=3, scale=1.0, fov=1.0, aabb=0)
-    pt = PathTracer(40, 24, ed.compile(CompData()), settings=st)
-    pt.dispatch(N.Constants(time=0.0, frame=1, aspect=float(np.float32(40) / np.float32(24)), last_clear=1), 3)
+    pt = G.tracer("c2", 40, 24, 3)
+    pt.dispatch(G.constants(40, 24), 3)
     with pytest.raises(N.NativeError) as e:
         pt.reduce(0)  # before pt_comm_init
     assert e.value.code == N.PT_ERR_STATE
@@ -467,17 +409,14 @@ def test_jit_tier_up_follows_value_edits(gpu):
     the rebuilt one is waited for.  Every image stays exact."""
     ed = scenes.c2_sphere_box_torus()
     cd = CompData()
-    prog = ed.compile(cd)
-    st = N.Settings(debug=0, bounces=3, scale=1.0, fov=1.0, aabb=0)
-    pt = PathTracer(40, 30, prog, settings=st, options={"kernel": "binned", "jit": 1, "jit_bake": 2})
-    c = N.Constants(time=0.0, frame=1, aspect=float(np.float32(40) / np.float32(30)), last_clear=1)
+    # (not G.tracer: it would wait for the values-baked build)
+    pt = PathTracer(40, 30, ed.compile(cd), settings=N.Settings(debug=0, bounces=3, scale=1.0, fov=1.0, aabb=0),
+                    options=KERNELS["binned_tier"])
 
     def check():
         pt.clear()
-        pt.dispatch(c, 2)
-        ref = O.OracleScene(ed.rows()).render(40, 30, O.Constants(0.0, 1, c.aspect, 1), O.Settings(0, 3, 1.0, 1.0, 0),
-                                              2)
-        assert np.array_equal(pt.read_image().view(np.uint32), ref.view(np.uint32))
+        pt.dispatch(G.constants(40, 30), 2)
+        assert G.same_bits(pt.read_image(), G.oracle_image(ed, 40, 30, 2, 3)) == 1.0
 
     check()
     pt.set_option("jit_wait", 1)
@@ -518,18 +457,15 @@ def test_shipped_scene_kernels_in_a_torch_process(gpu, name):
     import sys
 
     assert "torch" in sys.modules
-    ed = scenes.SCENES[name]()
-    prog = ed.compile(CompData())
-    st = N.Settings(debug=0, bounces=3, scale=1.0, fov=1.0, aabb=0)
-    pt = PathTracer(48, 32, prog, settings=st, options={"kernel": "binned", "jit": 1, "jit_bake": 2})
+    # (not G.tracer: the table kernel's build is read before the wait for the values-baked one)
+    pt = PathTracer(48, 32, scenes.SCENES[name]().compile(CompData()),
+                    settings=N.Settings(debug=0, bounces=3, scale=1.0, fov=1.0, aabb=0), options=KERNELS["binned_tier"])
     assert pt.get_option("jit_trace_waves") == 8 and pt.get_option("jit_shade_waves") == 8
     assert pt.get_option("jit_seconds") < 1.0  # (a cache hit, not a 5-25 s compile)
     pt.set_option("jit_wait", 1)
     assert pt.get_option("jit_tier_active") == 1.0
     assert pt.get_option("jit_trace_waves") == 8 and pt.get_option("jit_shade_waves") == 8
-    a = float(np.float32(48) / np.float32(32))
-    pt.dispatch(N.Constants(time=0.0, frame=1, aspect=a, last_clear=1), 2)
+    pt.dispatch(G.constants(48, 32), 2)
     gpu_img = pt.read_image()
     pt.close()
-    ref = O.OracleScene(ed.rows()).render(48, 32, O.Constants(0.0, 1, a, 1), O.Settings(0, 3, 1.0, 1.0, 0), 2)
-    assert np.array_equal(gpu_img.view(np.uint32), ref.view(np.uint32))
+    assert G.same_bits(gpu_img, G.oracle_image(name, 48, 32, 2, 3)) == 1.0

@@ -1,12 +1,12 @@
 """GPU: the sky (pt_set_sky) through every kernel variant,
-bit for bit against tests/skyref.py -- pyref's path arithmetic with the miss
+bit for bit against tests/camref.py -- pyref's path arithmetic with the miss
 term over the oracle's map() and bounds(), pinned to the oracle by
 tests/test_sky_ref.py.  Every comparison is view(np.uint32) equality of the
 whole image.
 
 The sky is sky_light((0.9, 0.8, 0.7), (0.25, 0.45, 0.9), sun towards
 (0.4, 0.7, -0.6), sun colour (8, 7, 5), sun angle 30 degrees).  The float32
-values sky_light returned go to the GPU and to skyref alike, so sky_light's
+values sky_light returned go to the GPU and to camref alike, so sky_light's
 own rounding is not under test here.  The cameras are test_gpu_camera.py's.
 """
 import ctypes
@@ -15,77 +15,23 @@ import functools
 import numpy as np
 import pytest
 
-import skyref
+import camref
+import gpuharness as G
 from compute_path_tracer_amd import _native as N
 from compute_path_tracer_amd import scenes
-from compute_path_tracer_amd.path_tracer import PathTracer, look_at_camera, sky_light
 from compute_path_tracer_amd.sdf_editor import CompData
-from oracle import oracle as O
+from gpuharness import ALL, EYE, LOOK, SKY, TARGET
 
 pytestmark = pytest.mark.gpu
-
-# the option table of test_gpu_parity.py
-KERNELS = {"simple": {"kernel": "simple", "jit": 0}, "wave": {"kernel": "wave", "jit": 0},
-           "jit": {"kernel": "wave", "jit": 1, "jit_bake": 0}, "binned": {"kernel": "binned", "jit": 0},
-           "binned_jit": {"kernel": "binned", "jit": 1, "jit_bake": 0},
-           "binned_bake": {"kernel": "binned", "jit": 1, "jit_bake": 1},
-           "binned_tier": {"kernel": "binned", "jit": 1, "jit_bake": 2},
-           "binned_trace_taps": {"kernel": "binned", "jit": 1, "jit_bake": 2, "shade_taps": 0}}
-ALL = ["simple", "wave", "jit", "binned", "binned_jit", "binned_bake", "binned_tier", "binned_trace_taps"]
-
-EYE, TARGET = (2.0, 1.5, -2.5), (0.0, 0.0, 0.0)
-LOOK = {"default": None, "pinhole": {}, "lens": {"aperture": 0.05, "focus": 3.0}}
-FRAME = LAST_CLEAR = 1
-SKY = dict(bottom=(0.9, 0.8, 0.7), top=(0.25, 0.45, 0.9), sun_direction=(0.4, 0.7, -0.6), sun_color=(8.0, 7.0, 5.0),
-           sun_angle=30.0)
-
-
-def _aspect(w, h):
-    return float(np.float32(w) / np.float32(h))
-
-
-def _sky():
-    return sky_light(**SKY)
-
-
-def _camera(kind):
-    return None if LOOK[kind] is None else look_at_camera(EYE, TARGET, **LOOK[kind])
 
 
 @functools.lru_cache(maxsize=None)
 def _ref(name, w, h, spp, bounces, kind="default", debug=0, sky=True):
-    """skyref's image, computed once per case and shared (read-only)."""
-    img = skyref.render(scenes.SCENES[name]().rows(), w, h, FRAME, LAST_CLEAR, _aspect(w, h), bounces, spp,
-                        debug=debug, camera=_camera(kind), sky=_sky() if sky else None)
+    """camref's image, computed once per case and shared (read-only)."""
+    img = camref.render(scenes.SCENES[name]().rows(), w, h, 1, 1, G.aspect(w, h), bounces, spp, debug=debug,
+                        camera=G.camera(kind), sky=G.sky() if sky else None)
     img.setflags(write=False)
     return img
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle(name, w, h, spp, bounces, debug=0):
-    """The sky-off image of the default camera, from the C oracle."""
-    img = O.OracleScene(scenes.SCENES[name]().rows()).render(
-        w, h, O.Constants(0.0, FRAME, _aspect(w, h), LAST_CLEAR), O.Settings(debug, bounces, 1.0, 1.0, 0), spp)
-    img.setflags(write=False)
-    return img
-
-
-def _tracer(name, w, h, bounces, kernel, debug=0, extra=None, prog=None):
-    prog = prog if prog is not None else scenes.SCENES[name]().compile(CompData())
-    opts = dict(KERNELS[kernel])
-    opts.update(extra or {})
-    pt = PathTracer(w, h, prog, settings=N.Settings(debug=debug, bounces=bounces, scale=1.0, fov=1.0, aabb=0),
-                    options=opts)
-    if opts["jit"]:
-        assert pt.get_option("jit_active") == 1.0, pt.jit_log()
-    if opts.get("jit_bake") == 2:  # wait for the values-baked build, so the test runs on it
-        pt.set_option("jit_wait", 1)
-        assert pt.get_option("jit_tier_active") == 1.0, pt.jit_log()
-    return pt
-
-
-def _constants(w, h):
-    return N.Constants(time=0.0, frame=FRAME, aspect=_aspect(w, h), last_clear=LAST_CLEAR)
 
 
 def _set_view(pt, kind):
@@ -95,27 +41,23 @@ def _set_view(pt, kind):
 
 def _render(name, w, h, spp, bounces, kernel, kind="default", debug=0, extra=None):
     """The GPU image with the test sky (and camera), and the dispatch's sky pass count."""
-    pt = _tracer(name, w, h, bounces, kernel, debug, extra)
+    pt = G.tracer(name, w, h, bounces, kernel, debug, extra)
     _set_view(pt, kind)
     sky = pt.set_sky(**SKY)
-    assert bytes(sky) == bytes(_sky())  # the values skyref gets
+    assert bytes(sky) == bytes(G.sky())  # the values camref gets
     got, off = pt.get_sky()
     assert bytes(got) == bytes(sky) and not off
-    pt.dispatch(_constants(w, h), spp)
+    pt.dispatch(G.constants(w, h), spp)
     img = pt.read_image()
     launches = pt.get_option("sky_launches")
     pt.close()
     return img, launches
 
 
-def _same_bits(a, b):
-    return float(np.mean(a.view(np.uint32) == b.view(np.uint32)))
-
-
 def _check_reference(ref, name, w, h, spp, bounces, kind="default", debug=0):
     """The reference is finite and shows the sky: it is not the sky-off image."""
     assert np.isfinite(ref).all() and ref[..., :3].mean() > 0
-    dark = _oracle(name, w, h, spp, bounces, debug) if kind == "default" else \
+    dark = G.oracle_image(name, w, h, spp, bounces, debug) if kind == "default" else \
         _ref(name, w, h, spp, bounces, kind, debug, sky=False)
     assert not np.array_equal(ref.view(np.uint32), dark.view(np.uint32))
 
@@ -133,7 +75,7 @@ def test_sky_every_kernel(gpu, case, kind, kernel):
     ref = _ref(name, w, h, spp, bounces, kind)
     _check_reference(ref, name, w, h, spp, bounces, kind)
     img, launches = _render(name, w, h, spp, bounces, kernel, kind)
-    exact = _same_bits(img, ref)
+    exact = G.same_bits(img, ref)
     print(f"{kernel} {name} {w}x{h} {kind}: bit-exact={exact:.5f} mean={ref[..., :3].mean():.5f} "
           f"sky passes={launches:.0f}")
     assert exact == 1.0
@@ -151,7 +93,7 @@ def test_sky_wide_scene(gpu, kernel):
     ref = _ref(name, w, h, spp, bounces)
     _check_reference(ref, name, w, h, spp, bounces)
     img, _ = _render(name, w, h, spp, bounces, kernel)
-    assert _same_bits(img, ref) == 1.0
+    assert G.same_bits(img, ref) == 1.0
 
 
 @pytest.mark.parametrize("kernel", ["binned_jit", "binned_tier"])
@@ -164,46 +106,46 @@ def test_sky_one_pixel_over_64_frames(gpu, kind, bin_lanes, kernel):
     colour region."""
     ref = _ref("c2", 8, 8, 70, 4, kind)
     _check_reference(ref, "c2", 8, 8, 70, 4, kind)
-    pt = _tracer("c2", 8, 8, 4, kernel, extra={"bin_lanes": bin_lanes})
+    pt = G.tracer("c2", 8, 8, 4, kernel, extra={"bin_lanes": bin_lanes})
     _set_view(pt, kind)
     pt.set_sky(**SKY)
-    pt.dispatch(_constants(8, 8), 70)
+    pt.dispatch(G.constants(8, 8), 70)
     img = pt.read_image()
     flags = (pt.get_option("gen_trace"), pt.get_option("gen_norec"), pt.get_option("sky_launches"))
     pt.close()
     assert flags == (1.0, 1.0, float(bin_lanes * 5))
-    assert _same_bits(img, ref) == 1.0
+    assert G.same_bits(img, ref) == 1.0
 
 
 @pytest.mark.parametrize("kernel", ["binned", "binned_jit"])
 def test_sky_several_chunks(gpu, kernel):
     """bin_samples 128 < 24 * 16: one frame per chunk, so two chunks per dispatch."""
     name, w, h, spp, bounces = "c3", 24, 16, 2, 8
-    pt = _tracer(name, w, h, bounces, kernel, extra={"bin_samples": 128})
+    pt = G.tracer(name, w, h, bounces, kernel, extra={"bin_samples": 128})
     pt.set_sky(**SKY)
-    pt.dispatch(_constants(w, h), spp)
+    pt.dispatch(G.constants(w, h), spp)
     img = pt.read_image()
     chunks, launches = pt.get_option("bin_chunks"), pt.get_option("sky_launches")
     pt.close()
     assert chunks == 2.0 and launches == 2.0 * (bounces + 1)
-    assert _same_bits(img, _ref(name, w, h, spp, bounces)) == 1.0
+    assert G.same_bits(img, _ref(name, w, h, spp, bounces)) == 1.0
 
 
 @pytest.mark.parametrize("kernel", ["simple", "jit", "binned_jit"])
 @pytest.mark.parametrize("debug", [1, 2, 3])
 def test_debug_views_ignore_the_sky(gpu, debug, kernel):
     """Views 1 and 2 never path trace and view 3 shows the segment count: the oracle's sky-off image."""
-    ref = _oracle("c3", 24, 16, 2, 8, debug)
+    ref = G.oracle_image("c3", 24, 16, 2, 8, debug)
     assert np.array_equal(_ref("c3", 24, 16, 2, 8, "default", debug).view(np.uint32), ref.view(np.uint32))
     img, launches = _render("c3", 24, 16, 2, 8, kernel, debug=debug)
     assert launches == 0.0
-    assert _same_bits(img, ref) == 1.0
+    assert G.same_bits(img, ref) == 1.0
 
 
 @pytest.mark.parametrize("kernel", ["simple", "jit", "binned_tier"])
 def test_clear_sky_restores_the_void(gpu, kernel):
     w, h, spp, bounces = 24, 16, 2, 8
-    pt = _tracer("c3", w, h, bounces, kernel)
+    pt = G.tracer("c3", w, h, bounces, kernel)
     sky, off = pt.get_sky()
     assert off and bytes(sky) == bytes(N.Sky())
     pt.set_sky(**SKY)
@@ -213,11 +155,11 @@ def test_clear_sky_restores_the_void(gpu, kernel):
     assert off and bytes(sky) == bytes(N.Sky())
     is_off = ctypes.c_int(-1)
     assert N.lib().pt_get_sky(pt._ctx, None, ctypes.byref(is_off)) == N.PT_OK and is_off.value == 1
-    pt.dispatch(_constants(w, h), spp)
+    pt.dispatch(G.constants(w, h), spp)
     img = pt.read_image()
     assert pt.get_option("sky_launches") == 0.0
     pt.close()
-    assert _same_bits(img, _oracle("c3", w, h, spp, bounces)) == 1.0
+    assert G.same_bits(img, G.oracle_image("c3", w, h, spp, bounces)) == 1.0
 
 
 @pytest.mark.parametrize("kernel", ["jit", "binned_tier"])
@@ -228,16 +170,16 @@ def test_sky_survives_resets_and_rebuilds(gpu, kernel):
     ed = scenes.SCENES["c2"]()
     cd = CompData()
     prog = ed.compile(cd)
-    pt = _tracer("c2", w, h, bounces, kernel, prog=prog)
+    pt = G.tracer(prog, w, h, bounces, kernel)
     sky = pt.set_sky(**SKY)
     ref = _ref("c2", w, h, spp, bounces)
 
     def check(want):
         pt.clear()
-        pt.dispatch(_constants(w, h), spp)
+        pt.dispatch(G.constants(w, h), spp)
         got, off = pt.get_sky()
         assert bytes(got) == bytes(sky) and not off
-        assert _same_bits(pt.read_image(), want) == 1.0
+        assert G.same_bits(pt.read_image(), want) == 1.0
 
     check(ref)
     pt.update(reset=True)
@@ -255,7 +197,7 @@ def test_sky_survives_resets_and_rebuilds(gpu, kernel):
         assert pt.get_option("jit_tier_active") == 0.0
         pt.set_option("jit_wait", 1)
         assert pt.get_option("jit_tier_active") == 1.0
-        edited = skyref.render(ed.rows(), w, h, FRAME, LAST_CLEAR, _aspect(w, h), bounces, spp, sky=_sky())
+        edited = camref.render(ed.rows(), w, h, 1, 1, G.aspect(w, h), bounces, spp, sky=G.sky())
         assert not np.array_equal(edited, ref)
         check(edited)
     pt.close()
@@ -270,21 +212,21 @@ def test_tile_split_with_sky_and_lens(gpu, kernel):
     ref = _ref("c3", w, h, spp, bounces, "lens")
     total = np.zeros((h, w, 4), np.float32)
     for rank in range(2):
-        pt = _tracer("c3", w, h, bounces, kernel)
+        pt = G.tracer("c3", w, h, bounces, kernel)
         pt.set_tiles(rank, 2)
         _set_view(pt, "lens")
         pt.set_sky(**SKY)
-        pt.dispatch(_constants(w, h), spp)
+        pt.dispatch(G.constants(w, h), spp)
         part = pt.read_image()
         pt.close()
         assert np.any(part != 0) and np.any(np.all(part == 0, axis=-1))  # owns some tiles, not all
         total += part
-    assert _same_bits(total, ref) == 1.0
+    assert G.same_bits(total, ref) == 1.0
 
 
 def test_invalid_skies_are_refused(gpu):
     w, h, spp, bounces = 24, 16, 2, 8
-    pt = _tracer("c3", w, h, bounces, "jit")
+    pt = G.tracer("c3", w, h, bounces, "jit")
     good = pt.set_sky(**SKY)
     L = N.lib()
 
@@ -307,10 +249,10 @@ def test_invalid_skies_are_refused(gpu):
     with pytest.raises(N.NativeError) as e:
         pt.set_sky(bad[4])  # a ready Sky goes to the library as it is
     assert e.value.code == N.PT_ERR_INVALID
-    pt.dispatch(_constants(w, h), spp)
+    pt.dispatch(G.constants(w, h), spp)
     img = pt.read_image()
     pt.close()
-    assert _same_bits(img, _ref("c3", w, h, spp, bounces)) == 1.0
+    assert G.same_bits(img, _ref("c3", w, h, spp, bounces)) == 1.0
 
 
 def test_sky_calls_mark_the_renderer_changed(gpu):
@@ -318,8 +260,8 @@ def test_sky_calls_mark_the_renderer_changed(gpu):
     image as for a settings change: render() after a sky change starts a
     fresh accumulation."""
     w, h, spp, bounces = 24, 16, 2, 8
-    pt = _tracer("c3", w, h, bounces, "jit")
-    for call in (lambda: pt.set_sky(**SKY), lambda: pt.set_sky(_sky()), pt.clear_sky):
+    pt = G.tracer("c3", w, h, bounces, "jit")
+    for call in (lambda: pt.set_sky(**SKY), lambda: pt.set_sky(G.sky()), pt.clear_sky):
         pt.changed = False
         call()
         assert pt.changed is True
@@ -332,7 +274,7 @@ def test_sky_calls_mark_the_renderer_changed(gpu):
     img = pt.read_image()
     pt.close()
     assert pt.constants.last_clear == spp
-    assert _same_bits(img, _ref("c3", w, h, spp, bounces)) == 1.0
+    assert G.same_bits(img, _ref("c3", w, h, spp, bounces)) == 1.0
 
 
 @pytest.mark.parametrize("kernel", ["simple", "jit", "binned", "binned_jit"])
@@ -340,17 +282,17 @@ def test_stats_with_a_sky(gpu, kernel):
     """The instrumented run counts every sample, leaves the image untouched,
     and counts the work it counted without a sky (the sky adds no counter)."""
     w, h, spp, bounces = 24, 16, 2, 8
-    pt = _tracer("c3", w, h, bounces, kernel)
-    dark = pt.stats(_constants(w, h), spp)
+    pt = G.tracer("c3", w, h, bounces, kernel)
+    dark = pt.stats(G.constants(w, h), spp)
     pt.set_sky(**SKY)
-    pt.dispatch(_constants(w, h), spp)
+    pt.dispatch(G.constants(w, h), spp)
     before = pt.read_image()
-    st = pt.stats(_constants(w, h), spp)
+    st = pt.stats(G.constants(w, h), spp)
     after = pt.read_image()
     pt.close()
     assert st["samples"] == w * h * spp
     assert np.array_equal(before.view(np.uint32), after.view(np.uint32))
-    assert _same_bits(after, _ref("c3", w, h, spp, bounces)) == 1.0
+    assert G.same_bits(after, _ref("c3", w, h, spp, bounces)) == 1.0
     # the work counters (samples .. rr_break, and the first shade pass's hits): the rest are wave clock
     # readings and wave-level tallies of the persistent waves' schedule, which differ between any two dispatches
     work = N.STAT_NAMES[:N.STAT_NAMES.index("rr_break") + 1] + ("shaded_first",)

@@ -1,26 +1,17 @@
-"""The sky on the CPU (no GPU): tests/skyref.py, the reference the GPU sky
-tests compare with, against the C oracle where the oracle can render (no
-sky), against the sky's formula on a scene where every ray misses, and the
-sky_light arithmetic of the Python mirror.
+"""The sky on the CPU (no GPU): tests/camref.py's render with a sky, the
+reference the GPU sky tests compare with, against the C oracle where the
+oracle can render (no sky), against the sky's formula on a scene where every
+ray misses, and the sky_light arithmetic of the Python mirror.
 """
-import functools
-
 import numpy as np
 import pytest
 
+import camref
+import gpuharness as G
 import pyref as P
-import skyref
 from compute_path_tracer_amd import scenes
-from oracle import oracle as O
 
 F = np.float32
-
-EYE, TARGET = (2.0, 1.5, -2.5), (0.0, 0.0, 0.0)  # the camera tests' pose
-LOOK = {"default": None, "pinhole": {}, "lens": {"aperture": 0.05, "focus": 3.0}}
-
-
-def _aspect(w, h):
-    return float(F(w) / F(h))
 
 
 def _sky_light(*args, **kw):
@@ -29,31 +20,11 @@ def _sky_light(*args, **kw):
     return sky_light(*args, **kw)
 
 
-def _camera(kind):
-    from compute_path_tracer_amd.path_tracer import look_at_camera
-
-    return None if LOOK[kind] is None else look_at_camera(EYE, TARGET, **LOOK[kind])
-
-
-def _test_sky():
-    """The sky of every GPU test (tests/test_gpu_sky.py)."""
-    return _sky_light((0.9, 0.8, 0.7), (0.25, 0.45, 0.9), (0.4, 0.7, -0.6), (8.0, 7.0, 5.0), 30.0)
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle(name, w, h, spp, bounces, debug=0):
-    rows = scenes.SCENES[name]().rows()
-    a = _aspect(w, h)
-    img = O.OracleScene(rows).render(w, h, O.Constants(0.0, 1, a, 1), O.Settings(debug, bounces, 1.0, 1.0, 0), spp)
-    img.setflags(write=False)
-    return img
-
-
 @pytest.mark.parametrize("name,w,h,spp,bounces", [("c2", 24, 16, 2, 4), ("c3", 24, 16, 2, 8)])
 def test_skyref_without_a_sky_equals_oracle(name, w, h, spp, bounces):
-    """skyref's render loop with sky=None is pto_render, bit for bit."""
-    got = skyref.render(scenes.SCENES[name]().rows(), w, h, 1, 1, _aspect(w, h), bounces, spp)
-    ref = _oracle(name, w, h, spp, bounces)
+    """The reference's render loop with sky=None is pto_render, bit for bit."""
+    got = camref.render(scenes.SCENES[name]().rows(), w, h, 1, 1, G.aspect(w, h), bounces, spp)
+    ref = G.oracle_image(name, w, h, spp, bounces)
     assert ref[..., :3].mean() > 0
     assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
 
@@ -63,24 +34,24 @@ def test_skyref_without_a_sky_equals_oracle(name, w, h, spp, bounces):
 def test_skyref_debug_views_equal_oracle(debug, with_sky):
     """The debug views, with a sky too: 1 and 2 never path trace, 3 shows the segment count."""
     w, h = 12, 8
-    got = skyref.render(scenes.SCENES["c3"]().rows(), w, h, 1, 1, _aspect(w, h), 8, 1, debug=debug,
-                        sky=_test_sky() if with_sky else None)
-    assert np.array_equal(got.view(np.uint32), _oracle("c3", w, h, 1, 8, debug).view(np.uint32))
+    got = camref.render(scenes.SCENES["c3"]().rows(), w, h, 1, 1, G.aspect(w, h), 8, 1, debug=debug,
+                        sky=G.sky() if with_sky else None)
+    assert np.array_equal(got.view(np.uint32), G.oracle_image("c3", w, h, 1, 8, debug).view(np.uint32))
 
 
 @pytest.mark.parametrize("sun_ahead", [False, True])
 def test_empty_scene_shows_the_sky_itself(sun_ahead):
     """No shape: every primary ray misses with throughput 1, so a texel is its
     own ray's sky radiance, mixed into the cleared image -- computed here from
-    the formula of DESIGN.md 3.25 in numpy float32, not through skyref.  The
+    the formula of DESIGN.md 3.25 in numpy float32, not through pyref.  The
     test sky's sun stands behind the default camera; a second sky puts one in
     view."""
     w, h = 16, 8
-    a = F(_aspect(w, h))
+    a = F(G.aspect(w, h))
     sky = _sky_light((0.9, 0.8, 0.7), (0.25, 0.45, 0.9), (0.2, 0.3, 1.0), (8.0, 7.0, 5.0), 15.0) if sun_ahead \
-        else _test_sky()
+        else G.sky()
     counts = {}
-    img = skyref.render(scenes.SCENES["empty"]().rows(), w, h, 1, 1, float(a), 4, 1, sky=sky, counts=counts)
+    img = camref.render(scenes.SCENES["empty"]().rows(), w, h, 1, 1, float(a), 4, 1, sky=sky, counts=counts)
     assert counts["miss"] == w * h
     bottom, top, sun_dir, sun_color = (np.array(list(v), np.float32) for v in (sky.bottom, sky.top, sky.sun_dir,
                                                                                sky.sun_color))
@@ -110,7 +81,7 @@ def test_empty_scene_shows_the_sky_itself(sun_ahead):
     assert img[h - 1, :, 2].mean() > img[0, :, 2].mean() and img[0, :, 0].mean() > img[h - 1, :, 0].mean()
 
 
-# samples whose path ended in a miss / of those, inside the sun's disc, as recorded when skyref was written
+# samples whose path ended in a miss / of those, inside the sun's disc, as recorded when the reference was written
 # (a wrong gradient moves no count, but a wrong sun test, a wrong segment direction or a lost miss does)
 COUNTS = [
     ("c2", 24, 16, 2, 4, "default", 637, 39),
@@ -130,17 +101,17 @@ def test_sky_cases_reach_the_sky_and_the_sun(name, w, h, spp, bounces, kind, mis
     """The GPU tests' cases: how many samples end in the sky and in the sun's
     disc, and how much of the image the sky changes."""
     rows = scenes.SCENES[name]().rows()
-    a = _aspect(w, h)
-    cam = _camera(kind)
+    a = G.aspect(w, h)
+    cam = G.camera(kind)
     counts = {}
-    img = skyref.render(rows, w, h, 1, 1, a, bounces, spp, camera=cam, sky=_test_sky(), counts=counts)
+    img = camref.render(rows, w, h, 1, 1, a, bounces, spp, camera=cam, sky=G.sky(), counts=counts)
     assert np.isfinite(img).all()
     assert (counts["miss"], counts["sun"]) == (miss, sun)
     assert sun >= 8
     if name == "c3":
         assert miss >= 100  # mostly later segments (c2's are mostly first segments)
     dark = {}
-    off = skyref.render(rows, w, h, 1, 1, a, bounces, spp, camera=cam, counts=dark)
+    off = camref.render(rows, w, h, 1, 1, a, bounces, spp, camera=cam, counts=dark)
     assert dark["miss"] == miss and dark["sun"] == 0  # the sky draws no random number: the paths are the same
     changed = float(np.mean(np.any(img.view(np.uint32) != off.view(np.uint32), axis=-1)))
     assert changed > (0.9 if name == "c2" else 0.2), changed
@@ -151,7 +122,7 @@ def test_sky_light_defaults_and_rounding():
     assert list(sky.top) == list(sky.bottom) == [0.5, 0.25, 0.125]  # top defaults to bottom: uniform ambient light
     assert list(sky.sun_color) == [0.0, 0.0, 0.0]
     assert sky.sun_cos == 1.0  # sun_angle 0
-    sky = _test_sky()
+    sky = G.sky()
     assert list(sky.bottom) == [float(F(v)) for v in (0.9, 0.8, 0.7)]
     assert list(sky.top) == [float(F(v)) for v in (0.25, 0.45, 0.9)]
     assert list(sky.sun_color) == [8.0, 7.0, 5.0]
