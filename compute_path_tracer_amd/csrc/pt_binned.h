@@ -36,7 +36,7 @@
 #endif
 #define PT_BINS (1 << PT_BIN_BITS)
 #define PT_BIN_NONE 0xffffffffu
-#define PT_AUX_MISS 0xffffffffu  // trace -> shade: PtRay q2.w of a position whose segment missed
+#define PT_AUX_MISS 0xffffffffu  // trace -> shade: a position whose segment missed (rec_miss / hq_miss)
 #define PT_BIN_BLOCK 256  // threads per block of the gen / bounds / scatter kernels
 // A pass's control words (PtPass.ctrl): [0] = its ray count, and the trace
 // pass's run cursors, one per share of the pass (PT_RUN_SHARDS, one per XCD),
@@ -54,8 +54,8 @@
 // of its segment (hit record), 64 B = four 16 B quads:
 //   q0 = (ro.x, ro.y, ro.z, rd.x)        ro: origin, or the hit point
 //   q1 = (rd.y, rd.z, thr.x, thr.y)
-//   q2 = (thr.z, rng, sid, aux)          sid: sample slot = frame * n_pix + local
-//                                        pixel; aux: a ray's own slot (its index
+//   q2 = (thr.z, rng, sid, aux)          sid: the sample's colour slot
+//                                        (colour_slot); aux: a ray's own slot (its index
 //                                        in its buffer), a hit record's material
 //                                        index, or PT_AUX_MISS (a miss writes
 //                                        only this quad, with the traced
@@ -71,9 +71,70 @@
 // The path's radiance (path_trace's `ret`) is not carried: it lives in the
 // sample's colour slot (zeroed by gen), which the shade pass updates when an
 // emission is added and which is final when the path ends.
+// The codec below the struct is the one place that implements this layout.
 struct PtRay {
     uint4 q[4];
 };
+static_assert(sizeof(PtRay) == 64 && sizeof(uint4) == 16 && sizeof(float) == sizeof(uint32_t), "PtRay: four 16 B quads");
+
+namespace pt {
+
+// q0..q2 of a ray or hit record, unpacked (q3 travels beside them: what it
+// holds depends on the record's kind)
+struct PathRec {
+    pt_f3 ro, rd, thr;
+    uint32_t rng, sid, aux;
+};
+__device__ __forceinline__ void rec_pack(const PathRec &r, uint4 &q0, uint4 &q1, uint4 &q2) {
+    q0 = make_uint4(__float_as_uint(r.ro.x), __float_as_uint(r.ro.y), __float_as_uint(r.ro.z), __float_as_uint(r.rd.x));
+    q1 = make_uint4(__float_as_uint(r.rd.y), __float_as_uint(r.rd.z), __float_as_uint(r.thr.x), __float_as_uint(r.thr.y));
+    q2 = make_uint4(__float_as_uint(r.thr.z), r.rng, r.sid, r.aux);
+}
+__device__ __forceinline__ PathRec rec_unpack(const uint4 &q0, const uint4 &q1, const uint4 &q2) {
+    return PathRec{pt_f3{__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z)},
+                   pt_f3{__uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y)},
+                   pt_f3{__uint_as_float(q1.z), __uint_as_float(q1.w), __uint_as_float(q2.x)}, q2.y, q2.z, q2.w};
+}
+// a record's q2 where the segment missed (taps in the trace pass)
+__device__ __forceinline__ uint4 rec_miss(uint32_t slot, uint32_t sid) { return make_uint4(slot, 0u, sid, PT_AUX_MISS); }
+__device__ __forceinline__ bool rec_is_miss(const uint4 &q2) { return q2.w == PT_AUX_MISS; }
+__device__ __forceinline__ uint32_t rec_miss_slot(const uint4 &q2) { return q2.x; }
+// q3 of a hit record (calc_normal's differences) and of a ray (check[] bits 0..63)
+__device__ __forceinline__ uint4 rec_normal(float dv0, float dv1, float dv2) {
+    return make_uint4(__float_as_uint(dv0), __float_as_uint(dv1), __float_as_uint(dv2), 0u);
+}
+__device__ __forceinline__ void rec_normal_of(const uint4 &q3, float &dv0, float &dv1, float &dv2) {
+    dv0 = __uint_as_float(q3.x), dv1 = __uint_as_float(q3.y), dv2 = __uint_as_float(q3.z);
+}
+__device__ __forceinline__ uint64_t rec_check_lo(const uint4 &q3) { return uint64_t(q3.x) | (uint64_t(q3.y) << 32); }
+
+// The hit quad (taps in the shade pass).  w: the traced ray's slot or, in
+// the first pass without records (gen_norec), its check[] bits 0..31.
+__device__ __forceinline__ uint4 hq_hit(float t, int mat, float tap_bnd, uint32_t w) {
+    return make_uint4(__float_as_uint(t), uint32_t(mat), __float_as_uint(tap_bnd), w);
+}
+__device__ __forceinline__ uint4 hq_miss(uint32_t slot) { return make_uint4(0u, PT_AUX_MISS, 0u, slot); }
+__device__ __forceinline__ bool hq_is_miss(const uint4 &hq) { return hq.y == PT_AUX_MISS; }
+__device__ __forceinline__ float hq_t(const uint4 &hq) { return __uint_as_float(hq.x); }
+__device__ __forceinline__ int hq_mat(const uint4 &hq) { return int(hq.y); }
+__device__ __forceinline__ float hq_tap_bound(const uint4 &hq) { return __uint_as_float(hq.z); }
+__device__ __forceinline__ uint32_t hq_slot(const uint4 &hq) { return hq.w; }
+// a quad's bits in float registers and back (the trace pass's staging)
+__device__ __forceinline__ float4 quad_as_float4(const uint4 &q) {
+    return make_float4(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z), __uint_as_float(q.w));
+}
+__device__ __forceinline__ uint4 quad_as_uint4(const float4 &q) {
+    return make_uint4(__float_as_uint(q.x), __float_as_uint(q.y), __float_as_uint(q.z), __float_as_uint(q.w));
+}
+// check[] bits 64..127 of a hit (PtPass.hitn, .zw)
+__device__ __forceinline__ float4 hitn_pack(uint64_t hi) {
+    return make_float4(0.0f, 0.0f, __uint_as_float(uint32_t(hi)), __uint_as_float(uint32_t(hi >> 32)));
+}
+__device__ __forceinline__ uint2 hitn_check_hi(const float4 &nd) {
+    return make_uint2(__float_as_uint(nd.z), __float_as_uint(nd.w));
+}
+
+}  // namespace pt
 
 struct PtPass {
     PtLaunch L;             // scene tables, image, frame0 / last_clear0 of this chunk
@@ -335,9 +396,11 @@ __device__ __forceinline__ uint64_t primary_box_skip(const PtLaunch &L, const pt
 
 __device__ __forceinline__ void store_ray(PtRay *r, const pt_f3 &ro, const pt_f3 &rd, const pt_f3 &thr, uint32_t rng,
                                           uint32_t sid, uint32_t aux, const uint4 &q3) {
-    r->q[0] = make_uint4(__float_as_uint(ro.x), __float_as_uint(ro.y), __float_as_uint(ro.z), __float_as_uint(rd.x));
-    r->q[1] = make_uint4(__float_as_uint(rd.y), __float_as_uint(rd.z), __float_as_uint(thr.x), __float_as_uint(thr.y));
-    r->q[2] = make_uint4(__float_as_uint(thr.z), rng, sid, aux);
+    uint4 q0, q1, q2;
+    rec_pack(PathRec{ro, rd, thr, rng, sid, aux}, q0, q1, q2);
+    r->q[0] = q0;
+    r->q[1] = q1;
+    r->q[2] = q2;
     r->q[3] = q3;
 }
 
@@ -373,6 +436,22 @@ __device__ __forceinline__ void gen_sample(uint32_t frames, uint32_t p, uint32_t
 // first pass's position is its sample's slot (gen_sample) and a pixel's
 // frames lie in one run for the fold.
 __device__ __forceinline__ uint32_t colour_slot(uint32_t frames, uint32_t f, uint32_t pl) { return pl * frames + f; }
+// The first pass's sample (frame f of the chunk, local pixel pl): its pixel,
+// camera ray, rng and colour slot -- the one mapping the makers of a primary
+// ray of the binned passes use (gen, and shade pass 0 and the sky pass when
+// they make the traced ray again; the first trace pass keeps the same three
+// steps written out, bin_trace_body stage).  The launch's scalars are
+// arguments so a caller can pass them through its own asm barrier
+// (bin_shade_body).
+template <int CAM>
+__device__ __forceinline__ void first_sample(int rank, int nranks, int tiles_x, int width, int height, float aspect,
+                                             float fov, int32_t frame0, int cam_mode, const pt_camera &cam,
+                                             uint32_t frames, uint32_t f, uint32_t pl, int &x, int &y, uint32_t &rng,
+                                             pt_f3 &ro, pt_f3 &rd, uint32_t &sid) {
+    pixel_of(rank, nranks, tiles_x, pl, x, y);
+    camera_ray<CAM>(x, y, int32_t(uint32_t(frame0) + f), width, height, aspect, fov, cam_mode, cam, rng, ro, rd);
+    sid = colour_slot(frames, f, pl);
+}
 
 // gen: camera ray + bounds() of every (frame, pixel) of the chunk
 // (MapBounds<Map>: the generic box loop, or the scene kernels' straight-line
@@ -388,7 +467,7 @@ __device__ __forceinline__ void bin_gen_body(const PtPass &P) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t f = i / npix, pl = i - f * npix;
         int x, y;
-        pixel_of(L, pl, x, y);
+        pixel_of(L, pl, x, y);  // (ahead of first_sample: a slot outside the image makes no ray)
         const bool live = x < L.width && y < L.height;
         // the first pass's list in generation order (the host takes this path
         // only when every tile is full, so every slot is live)
@@ -397,14 +476,13 @@ __device__ __forceinline__ void bin_gen_body(const PtPass &P) {
             if (!P.gen_order) P.key[i] = PT_BIN_NONE;
             continue;
         }
-        uint32_t rng;
+        uint32_t rng, sid;
         pt_f3 ro, rd;
-        camera_ray<CAM>(x, y, int32_t(uint32_t(L.frame0) + f), L.width, L.height, L.aspect, L.fov, L.cam_mode, L.cam,
-                        rng, ro, rd);
+        first_sample<CAM>(L.rank, L.nranks, L.tiles_x, L.width, L.height, L.aspect, L.fov, L.frame0, L.cam_mode, L.cam,
+                          uint32_t(P.frames), f, pl, x, y, rng, ro, rd, sid);
         st.add(PT_ST_SAMPLES);
         const uint4 m = MapBounds<Map>::template mask<ST>(L, ro, rd, st);
         const BinProbe bp = P.gen_order ? BinProbe{0u, 0ull, 0ull} : bin_probe(P, m);  // (before the stores)
-        const uint32_t sid = colour_slot(uint32_t(P.frames), f, pl);
         store_ray(P.rin + i, ro, rd, pt_f3{1.0f, 1.0f, 1.0f}, rng, sid, i, make_uint4(m.x, m.y, 0u, 0u));
         P.color[sid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the path's radiance (ret) starts at 0
         if (wide_of<Map>(P)) P.mask_hi[i] = make_uint2(m.z, m.w);
@@ -462,26 +540,26 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
     // record (TAPS = true)
     auto shade_one = [&](uint32_t i, const uint4 &q0, const uint4 &q1, const uint4 &q2, const uint4 &q3,
                          const uint2 &hi, const uint4 &hq) {
-        pt_f3 ro{__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z)};
-        pt_f3 rd{__uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y)};
-        pt_f3 thr{__uint_as_float(q1.z), __uint_as_float(q1.w), __uint_as_float(q2.x)};
+        const PathRec rec = rec_unpack(q0, q1, q2);
+        pt_f3 ro = rec.ro, rd = rec.rd, thr = rec.thr;
         pt_f3 ret{0.0f, 0.0f, 0.0f};  // this segment's emission (added to the colour slot below)
-        uint32_t rng = q2.y;
-        const uint32_t sid = q2.z;
-        const int mat = int(TAPS ? q2.w : hq.y);
+        uint32_t rng = rec.rng;
+        const uint32_t sid = rec.sid;
+        const int mat = TAPS ? int(rec.aux) : hq_mat(hq);
         int seg = P.bounce;
         // taps in the trace pass: q3 = calc_normal's differences
-        float dv0 = __uint_as_float(q3.x), dv1 = __uint_as_float(q3.y), dv2 = __uint_as_float(q3.z);
+        float dv0, dv1, dv2;
+        rec_normal_of(q3, dv0, dv1, dv2);
         if constexpr (!TAPS) {
             // the hit point: calc_point's f32 steps with the trace's t
             // (pt_path.h after_map), so the same bits
-            const float t = __uint_as_float(hq.x);
+            const float t = hq_t(hq);
             ro = pt_f3{ro.x + rd.x * t, ro.y + rd.y * t, ro.z + rd.z * t};
             // (the taps' counters go to their own half of the stats buffer:
             // pt_dispatch_stats sums both, bench.py splits the flops by pass)
             // the ray's check[] bits 0..63 (q3.xy) and 64..127 (hi)
-            Check ck{uint64_t(q3.x) | (uint64_t(q3.y) << 32), uint64_t(hi.x) | (uint64_t(hi.y) << 32)};
-            const float bnd = __uint_as_float(hq.z);
+            Check ck{rec_check_lo(q3), uint64_t(hi.x) | (uint64_t(hi.y) << 32)};
+            const float bnd = hq_tap_bound(hq);
             // bnd widened by the taps' spread (two taps are at most 2e apart,
             // plus their coordinates' rounding): the first tap's tests against
             // it leave in `live` every shape any tap may need
@@ -545,7 +623,7 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         if constexpr (TAPS) {
             const uint4 q0 = P.rout[i].q[0], q1 = P.rout[i].q[1], q2 = P.rout[i].q[2], q3 = P.rout[i].q[3];
-            if (q2.w == PT_AUX_MISS) P.key[i] = PT_BIN_NONE;  // the path ended in the trace pass
+            if (rec_is_miss(q2)) P.key[i] = PT_BIN_NONE;  // the path ended in the trace pass
             else shade_one(i, q0, q1, q2, q3, make_uint2(0u, 0u), q3);
         } else {
             uint4 hq = P.hq[i];
@@ -553,7 +631,7 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
             // the compiler loads .yz, tests, then loads .xw inside the
             // branch -- a second round trip before the ray's gather)
             __asm__ volatile("" : "+v"(hq.x), "+v"(hq.y), "+v"(hq.z), "+v"(hq.w));
-            if (hq.y == PT_AUX_MISS) {
+            if (hq_is_miss(hq)) {
                 P.key[i] = PT_BIN_NONE;  // the path ended in the trace pass
                 continue;
             }
@@ -575,18 +653,15 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
                 uint32_t f, pl;
                 gen_sample(nf, i, f, pl);
                 int x, y;
-                pixel_of(rk, nr, tx, pl, x, y);
-                uint32_t rg;
-                pt_f3 o, d;
+                PathRec r{{}, {}, pt_f3{1.0f, 1.0f, 1.0f}, 0u, 0u, i};
                 // (the camera itself straight from the launch block: only a
                 // posed camera's path reads it)
-                camera_ray<CAM>(x, y, int32_t(uint32_t(L.frame0) + f), cw, chh, ca, cf, L.cam_mode, L.cam, rg, o, d);
-                q0 = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
-                q1 = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(1.0f), __float_as_uint(1.0f));
-                q2 = make_uint4(__float_as_uint(1.0f), rg, colour_slot(nf, f, pl), i);
-                q3 = make_uint4(hq.w, 0u, 0u, 0u);
+                first_sample<CAM>(rk, nr, tx, cw, chh, ca, cf, L.frame0, L.cam_mode, L.cam, nf, f, pl, x, y, r.rng, r.ro,
+                                  r.rd, r.sid);
+                rec_pack(r, q0, q1, q2);
+                q3 = make_uint4(hq_slot(hq), 0u, 0u, 0u);  // (gen_norec: the ray's check[] bits)
             } else {
-                const PtRay *r = P.rin + hq.w;
+                const PtRay *r = P.rin + hq_slot(hq);
                 q0 = r->q[0];
                 q1 = r->q[1];
                 q2 = r->q[2];
@@ -594,8 +669,7 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
             }
             uint2 hi = make_uint2(0u, 0u);
             if (wide_of<Map>(P)) {
-                const float4 nd = P.hitn[i];
-                hi = make_uint2(__float_as_uint(nd.z), __float_as_uint(nd.w));
+                hi = hitn_check_hi(P.hitn[i]);
             }
             shade_one(i, q0, q1, q2, q3, hi, hq);
         }
@@ -779,6 +853,7 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
     if (!GEN && uint32_t(lane) < nc) nslot = P.idx[nb + uint32_t(lane)];
     // staged window: lane j holds the ray of binned position wbase + j
     uint32_t wbase = 0u, wcnt = 0u, wtake = 0u;
+    // (q0..q2 in float registers: as uint4 the compiled trace kernels order the park's loads and waits differently)
     float4 s0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), s1 = s0, s2 = s0;
     uint4 s3 = make_uint4(0u, 0u, 0u, 0u);
     uint2 sh = make_uint2(0u, 0u);
@@ -789,38 +864,36 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
         wtake = 0u;
         in_lds = false;
         if (GEN && uint32_t(lane) < wcnt) {
-            const uint32_t i = wbase + uint32_t(lane), npix = uint32_t(P.n_pix);
+            const uint32_t i = wbase + uint32_t(lane);
             uint32_t f, pl;
             gen_sample(uint32_t(P.frames), i, f, pl);
-            const uint32_t sid = colour_slot(uint32_t(P.frames), f, pl);  // (= i)
-            (void)npix;
+            // (aux: its slot; sid = i too)
+            PathRec r{{}, {}, pt_f3{1.0f, 1.0f, 1.0f}, 0u, colour_slot(uint32_t(P.frames), f, pl), i};
+            // (first_sample's steps written out: through it, the 124-entry scene's first pass gains 20 B of scratch)
             int x, y;
             pixel_of(L, pl, x, y);
-            uint32_t rg;
-            pt_f3 o, d;
             // (fov through an empty asm: normalize's fov * fov, hoisted out of
             // the persistent loop, held a register there and spilled)
             float fov = L.fov;
             __asm__ volatile("" : "+v"(fov));
             camera_ray<CAM>(x, y, int32_t(uint32_t(L.frame0) + f), L.width, L.height, L.aspect, fov, L.cam_mode, L.cam,
-                            rg, o, d);
+                            r.rng, r.ro, r.rd);
             st.add(PT_ST_SAMPLES);
             // the boxes no camera ray of the window can hit (every lane of a
             // full window is here, as the skip's wave reductions need)
-            const uint64_t skip = wcnt == 64u ? primary_box_skip(L, o, d) : 0ull;
-            const uint4 m = MapBounds<Map>::template mask_skip<ST>(L, o, d, skip, st);
-            s0 = make_float4(o.x, o.y, o.z, d.x);
-            s1 = make_float4(d.y, d.z, 1.0f, 1.0f);
-            s2 = make_float4(1.0f, __uint_as_float(rg), __uint_as_float(sid), __uint_as_float(i));  // (aux: its slot)
+            const uint64_t skip = wcnt == 64u ? primary_box_skip(L, r.ro, r.rd) : 0ull;
+            const uint4 m = MapBounds<Map>::template mask_skip<ST>(L, r.ro, r.rd, skip, st);
+            uint4 q0, q1, q2;
+            rec_pack(r, q0, q1, q2);
+            s0 = quad_as_float4(q0), s1 = quad_as_float4(q1), s2 = quad_as_float4(q2);
             s3 = make_uint4(m.x, m.y, 0u, 0u);
             sh = make_uint2(m.z, m.w);
         } else if (uint32_t(lane) < wcnt) {
             const uint32_t slot = nslot;
             const uint4 *v = reinterpret_cast<const uint4 *>(P.rin + slot);
-            const uint4 a = v[0], b = v[1], c = v[2];
-            s0 = make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w));
-            s1 = make_float4(__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w));
-            s2 = make_float4(__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z), __uint_as_float(c.w));
+            s0 = quad_as_float4(v[0]);
+            s1 = quad_as_float4(v[1]);
+            s2 = quad_as_float4(v[2]);
             s3 = v[3];
             if (wide_of<Map>(P)) sh = P.mask_hi[slot];
         }
@@ -848,19 +921,15 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
                     P.color[sid] = make_float4(c.x, c.y, c.z, 0.0f);
                 }
                 // (.x: the traced ray's slot, for the sky pass -- pt_kernel.hip pt_bin_sky_kernel)
-                if constexpr (TAPS) P.rout[pos].q[2] = make_uint4(slot, 0u, sid, PT_AUX_MISS);
-                else P.hq[pos] = make_uint4(0u, PT_AUX_MISS, 0u, slot);
+                if constexpr (TAPS) P.rout[pos].q[2] = rec_miss(slot, sid);
+                else P.hq[pos] = hq_miss(slot);
                 if constexpr (GEN) P.color[sid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (no gen pass zeroed it)
             } else {
                 if constexpr (TAPS) {  // hit record: hit point + normal differences
-                    store_ray(P.rout + pos, ro, rd, thr, rng, sid, uint32_t(mat),
-                              make_uint4(__float_as_uint(dv0), __float_as_uint(dv1), __float_as_uint(dv2), 0u));
-                } else {  // hit quad: t, material, tap bound, slot (bin_shade_body)
-                    P.hq[pos] = make_uint4(__float_as_uint(t), uint32_t(mat), __float_as_uint(dv0),
-                                           GEN && P.gen_norec ? uint32_t(ck.lo) : slot);
-                    if (wide_of<Map>(P))
-                        P.hitn[pos] = make_float4(0.0f, 0.0f, __uint_as_float(uint32_t(ck.hi)),
-                                                  __uint_as_float(uint32_t(ck.hi >> 32)));
+                    store_ray(P.rout + pos, ro, rd, thr, rng, sid, uint32_t(mat), rec_normal(dv0, dv1, dv2));
+                } else {  // hit quad: t, material, tap bound (in dv0), slot (bin_shade_body)
+                    P.hq[pos] = hq_hit(t, mat, dv0, GEN && P.gen_norec ? uint32_t(ck.lo) : slot);
+                    if (wide_of<Map>(P)) P.hitn[pos] = hitn_pack(ck.hi);
                 }
             }
             state = ST_FREE;
@@ -875,16 +944,13 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
         const bool mapping_now = state == ST_MARCH || (TAPS && state == ST_NORMAL);
         const bool in_win = uint32_t(lane) < wcnt;
         ck.alo = wave_or_u64((mapping_now ? ck.lo : 0ull) |
-                             (in_win ? (uint64_t(s3.x) | (uint64_t(s3.y) << 32)) : 0ull));
+                             (in_win ? rec_check_lo(s3) : 0ull));
         ck.ahi = wide_of<Map>(P) ? wave_or_u64((mapping_now ? ck.hi : 0ull) |
                                       (in_win ? (uint64_t(sh.x) | (uint64_t(sh.y) << 32)) : 0ull))
                         : 0ull;
-        W[0][lane] = make_uint4(__float_as_uint(s0.x), __float_as_uint(s0.y), __float_as_uint(s0.z),
-                                __float_as_uint(s0.w));
-        W[1][lane] = make_uint4(__float_as_uint(s1.x), __float_as_uint(s1.y), __float_as_uint(s1.z),
-                                __float_as_uint(s1.w));
-        W[2][lane] = make_uint4(__float_as_uint(s2.x), __float_as_uint(s2.y), __float_as_uint(s2.z),
-                                __float_as_uint(s2.w));
+        W[0][lane] = quad_as_uint4(s0);
+        W[1][lane] = quad_as_uint4(s1);
+        W[2][lane] = quad_as_uint4(s2);
         W[3][lane] = s3;
         if constexpr (MapWide<Map>::v != 0)
             if (wide_of<Map>(P)) W[4][lane] = make_uint4(sh.x, sh.y, 0u, 0u);
@@ -895,12 +961,9 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
             // here nor gathered there)
             if (in_win && !P.gen_norec) {
                 uint4 *r = reinterpret_cast<uint4 *>(P.rin + wbase + uint32_t(lane));
-                r[0] = make_uint4(__float_as_uint(s0.x), __float_as_uint(s0.y), __float_as_uint(s0.z),
-                                  __float_as_uint(s0.w));
-                r[1] = make_uint4(__float_as_uint(s1.x), __float_as_uint(s1.y), __float_as_uint(s1.z),
-                                  __float_as_uint(s1.w));
-                r[2] = make_uint4(__float_as_uint(s2.x), __float_as_uint(s2.y), __float_as_uint(s2.z),
-                                  __float_as_uint(s2.w));
+                r[0] = quad_as_uint4(s0);
+                r[1] = quad_as_uint4(s1);
+                r[2] = quad_as_uint4(s2);
                 r[3] = s3;
                 // (check[] bits 64..127 need no copy here: the shade pass
                 // takes a hit's from its hitn entry, P.hitn)
@@ -924,37 +987,22 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
             const int src = int(wtake) + r;
             const bool got = state == ST_FREE && uint32_t(r) < take;
             if (!in_lds) park();  // first refill from this window
-            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;
-            float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f;
-            uint32_t d0 = 0u, d1 = 0u, d2 = 0u, d3 = 0u, e0 = 0u, e1 = 0u;
             if (got) {
-                const uint4 wa = W[0][src], wb = W[1][src], wc = W[2][src], wd = W[3][src];
-                a0 = __uint_as_float(wa.x), a1 = __uint_as_float(wa.y), a2 = __uint_as_float(wa.z);
-                a3 = __uint_as_float(wa.w);
-                b0 = __uint_as_float(wb.x), b1 = __uint_as_float(wb.y), b2 = __uint_as_float(wb.z);
-                b3 = __uint_as_float(wb.w);
-                c0 = __uint_as_float(wc.x), c1 = __uint_as_float(wc.y), c2 = __uint_as_float(wc.z);
-                c3 = __uint_as_float(wc.w);
-                d0 = wd.x, d1 = wd.y, d2 = wd.z, d3 = wd.w;
+                const PathRec r = rec_unpack(W[0][src], W[1][src], W[2][src]);
+                ro = r.ro;
+                rd = r.rd;
+                thr = r.thr;
+                rng = r.rng;
+                sid = r.sid;
+                slot = r.aux;  // (a ray's aux: its slot)
+                ck.lo = rec_check_lo(W[3][src]);
+                ck.hi = 0ull;
                 if constexpr (MapWide<Map>::v != 0) {
                     if (wide_of<Map>(P)) {
                         const uint4 we = W[4][src];
-                        e0 = we.x;
-                        e1 = we.y;
+                        ck.hi = uint64_t(we.x) | (uint64_t(we.y) << 32);
                     }
                 }
-            }
-            if (got) {
-                ro = pt_f3{a0, a1, a2};
-                rd = pt_f3{a3, b0, b1};
-                thr = pt_f3{b2, b3, c0};
-                rng = __float_as_uint(c1);
-                sid = __float_as_uint(c2);
-                slot = __float_as_uint(c3);  // (a ray's aux: its slot)
-                ck.lo = uint64_t(d0) | (uint64_t(d1) << 32);
-                (void)d2;
-                (void)d3;
-                ck.hi = uint64_t(e0) | (uint64_t(e1) << 32);
                 pos = wbase + uint32_t(src);
                 t = 0.0f;
                 step = 0;
@@ -1052,10 +1100,7 @@ __device__ __forceinline__ void bin_fold_body(const PtPass &P) {
                 for (uint32_t k = 0u; k < sn; ++k) {
                     const float4 c = tile[t][k];
                     const int32_t lc = int32_t(uint32_t(L.last_clear0) + f0 + s0 + k);
-                    const float w = 1.0f / float(lc + 1), omw = 1.0f - w;
-                    ar = ar * omw + c.x * w;
-                    ag = ag * omw + c.y * w;
-                    ab = ab * omw + c.z * w;
+                    mix_frame(ar, ag, ab, pt_f3{c.x, c.y, c.z}, lc);
                 }
             }
         }

@@ -30,18 +30,12 @@ enum : int { ST_FREE = 0, ST_BOUNDS = 1, ST_MARCH = 2, ST_NORMAL = 3, ST_SHADE =
 // where they are used -- kernel arguments in scalar registers, never per-lane
 // state.  The lens draws its two numbers directly after the jitter's, and
 // the rng it leaves is the one the path goes on with.
+// The camera of a sample whose scaled uv is (ux, uy) -- what camera_ray runs
+// once the jitter and calc_uv have formed them: the fixed pinhole in its own
+// code path, or the posed basis and, for PT_CAM_LENS, the lens.
 template <int CAM = PT_CAMK_ANY>
-__device__ __forceinline__ void camera_ray(int x, int y, int32_t frame, int width, int height, float aspect, float fov,
-                                           int cam_mode, const pt_camera &cam, uint32_t &rng, pt_f3 &ro, pt_f3 &rd) {
-    rng = pt_gen_rng(x, y, frame, width, height);
-    float jx = pt_random01(rng);
-    float jy = pt_random01(rng);
-    jx = jx - 0.5f;
-    jy = jy - 0.5f;
-    float ux = (float(x) + jx) / float(width), uy = (float(y) + jy) / float(height);
-    ux = ux * 2.0f - 1.0f;
-    uy = uy * 2.0f - 1.0f;
-    ux *= aspect;
+__device__ __forceinline__ void camera_from_uv(float ux, float uy, float fov, int cam_mode, const pt_camera &cam,
+                                               uint32_t &rng, pt_f3 &ro, pt_f3 &rd) {
     if (CAM == PT_CAMK_FIXED || (CAM == PT_CAMK_ANY && cam_mode == PT_CAM_DEFAULT)) {
         rd = pt_normalize(pt_f3{ux, uy, fov});
         ro = pt_f3{0.0f, 0.0f, -3.0f};
@@ -67,6 +61,20 @@ __device__ __forceinline__ void camera_ray(int x, int y, int32_t frame, int widt
                    (ro.z + right[2] * lx) + up[2] * ly};
         rd = pt_normalize(pt_f3{pf.x - ro.x, pf.y - ro.y, pf.z - ro.z});
     }
+}
+template <int CAM = PT_CAMK_ANY>
+__device__ __forceinline__ void camera_ray(int x, int y, int32_t frame, int width, int height, float aspect, float fov,
+                                           int cam_mode, const pt_camera &cam, uint32_t &rng, pt_f3 &ro, pt_f3 &rd) {
+    rng = pt_gen_rng(x, y, frame, width, height);
+    float jx = pt_random01(rng);
+    float jy = pt_random01(rng);
+    jx = jx - 0.5f;
+    jy = jy - 0.5f;
+    float ux = (float(x) + jx) / float(width), uy = (float(y) + jy) / float(height);
+    ux = ux * 2.0f - 1.0f;
+    uy = uy * 2.0f - 1.0f;
+    ux *= aspect;
+    camera_from_uv<CAM>(ux, uy, fov, cam_mode, cam, rng, ro, rd);
 }
 
 // Radiance of the sky (pt_set_sky) along direction rd: the
@@ -121,7 +129,7 @@ __device__ __forceinline__ bool ray_box(const PtAabb &bx, float ox, float oy, fl
 
 // The same test with the divisions as pt_div_rcp from per-ray reciprocals
 // (y = RN(1/d)); bit-identical results when the pt_div_*_ok guards hold for
-// the ray and the box (bounds_fast in pt_binned.h).
+// the ray and the box (bounds_mask in pt_binned.h).
 __device__ __forceinline__ bool ray_box_rcp(const PtAabb &bx, float ox, float oy, float oz, float dx, float dy,
                                             float dz, float yx, float yy, float yz) {
     const float tminx = pt_div_rcp(bx.bmin[0] - ox, dx, yx), tmaxx = pt_div_rcp(bx.bmax[0] - ox, dx, yx);
@@ -344,6 +352,15 @@ __device__ __forceinline__ pt_f3 final_color(int debug, int seg, int bounces, co
         return pt_f3{v, v, v};
     }
     return ret;
+}
+
+// One frame into a texel's running colour: mix(last, colour, 1 / (last_clear
+// + 1)) as x * (1 - w) + y * w (test_compute.glsl:242-245).
+__device__ __forceinline__ void mix_frame(float &ar, float &ag, float &ab, const pt_f3 &colour, int32_t last_clear) {
+    const float w = 1.0f / float(last_clear + 1), omw = 1.0f - w;
+    ar = ar * omw + colour.x * w;
+    ag = ag * omw + colour.y * w;
+    ab = ab * omw + colour.z * w;
 }
 
 }  // namespace pt
