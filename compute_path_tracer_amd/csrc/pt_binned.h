@@ -106,7 +106,7 @@ __device__ __forceinline__ uint4 rec_normal(float dv0, float dv1, float dv2) {
 __device__ __forceinline__ void rec_normal_of(const uint4 &q3, float &dv0, float &dv1, float &dv2) {
     dv0 = __uint_as_float(q3.x), dv1 = __uint_as_float(q3.y), dv2 = __uint_as_float(q3.z);
 }
-__device__ __forceinline__ uint64_t rec_check_lo(const uint4 &q3) { return uint64_t(q3.x) | (uint64_t(q3.y) << 32); }
+__device__ __forceinline__ uint64_t rec_check_lo(const uint4 &q3) { return check_half(q3.x, q3.y); }
 
 // The hit quad (taps in the shade pass).  w: the traced ray's slot or, in
 // the first pass without records (gen_norec), its check[] bits 0..31.
@@ -208,7 +208,7 @@ __device__ __forceinline__ BinProbe bin_probe(const PtPass &P, const uint4 &m) {
     b.e = 0ull;
     b.v = 0ull;
     if (P.btab) {
-        b.e = ((unsigned long long)m.y << 32 | m.x) + 1ull;  // (0: a free slot)
+        b.e = check_half(m.x, m.y) + 1ull;  // (0: a free slot)
         // (a plain load: a slot only ever goes from 0 to its set, so a stale
         // 0 just sends the lane to the CAS, which returns the slot's set)
         if (b.e != 0ull) b.v = P.btab[b.h];
@@ -248,8 +248,7 @@ template <bool ST>
 __device__ __forceinline__ uint4 bounds_mask(const PtLaunch &L, const pt_f3 &ro, const pt_f3 &rd, Stats<ST> &st) {
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     const caabb_ptr boxes = (caabb_ptr)L.aabbs;
-    const bool fast = L.fast_bounds != 0 && pt_div_coord_ok(ro.x) && pt_div_coord_ok(ro.y) &&
-                      pt_div_coord_ok(ro.z) && pt_div_dir_ok(rd.x) && pt_div_dir_ok(rd.y) && pt_div_dir_ok(rd.z);
+    const bool fast = L.fast_bounds != 0 && ray_in_guard(ro, rd);
     if (fast) {
         if constexpr (ST)
             if (first_active_lane()) st.add(PT_ST_BOUNDS_WAVES);
@@ -260,7 +259,7 @@ __device__ __forceinline__ uint4 bounds_mask(const PtLaunch &L, const pt_f3 &ro,
 #pragma unroll 4  // scalar box loads issued ahead of their slab tests
         for (int b = 0; b < L.n_aabb; ++b) {
             const PtAabb bx = boxes[b];
-            if (ray_box_ulp<false>(bx, ro.x, ro.y, ro.z, yx, yy, yz, gapu)) w[bx.back >> 5] |= 1u << (bx.back & 31);
+            if (ray_box_ulp<false>(bx, ro.x, ro.y, ro.z, yx, yy, yz, gapu)) check_set(w, bx.back);
         }
         if (__builtin_expect(__ballot(!(gapu > PT_ULP_MARGIN)) != 0ull, 0)) {
             if constexpr (ST)
@@ -268,8 +267,7 @@ __device__ __forceinline__ uint4 bounds_mask(const PtLaunch &L, const pt_f3 &ro,
             uint32_t v[4] = {0u, 0u, 0u, 0u};
             for (int b = 0; b < L.n_aabb; ++b) {
                 const PtAabb bx = boxes[b];
-                if (ray_box_rcp(bx, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, yx, yy, yz))
-                    v[bx.back >> 5] |= 1u << (bx.back & 31);
+                if (ray_box_rcp(bx, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, yx, yy, yz)) check_set(v, bx.back);
             }
             if (!(gapu > PT_ULP_MARGIN))
                 for (int k = 0; k < 4; ++k) w[k] = v[k];
@@ -277,7 +275,7 @@ __device__ __forceinline__ uint4 bounds_mask(const PtLaunch &L, const pt_f3 &ro,
     } else {
         for (int b = 0; b < L.n_aabb; ++b) {
             const PtAabb bx = boxes[b];
-            if (ray_box(bx, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z)) w[bx.back >> 5] |= 1u << (bx.back & 31);
+            if (ray_box(bx, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z)) check_set(w, bx.back);
         }
     }
     st.add(PT_ST_SEGMENTS);
@@ -350,8 +348,7 @@ __device__ __forceinline__ uint64_t primary_box_skip(const PtLaunch &L, const pt
     // the row-broadcast scans read every lane: with a partial EXEC the
     // inactive lanes' stale values could make a box look missed
     if (__builtin_amdgcn_read_exec() != ~0ull) return 0ull;
-    const bool fast = pt_div_coord_ok(ro.x) && pt_div_coord_ok(ro.y) && pt_div_coord_ok(ro.z) &&
-                      pt_div_dir_ok(rd.x) && pt_div_dir_ok(rd.y) && pt_div_dir_ok(rd.z);
+    const bool fast = ray_in_guard(ro, rd);  // (bounds()'s own predicate, as the proof needs)
     const uint64_t fm = __ballot(fast);
     if (fm == 0ull) return 0ull;
     // the origin of the first fast lane, and no fast lane with another one
@@ -412,16 +409,6 @@ __device__ __forceinline__ void hist_flush(const uint32_t *lh, uint32_t *hist) {
     __syncthreads();
     for (int b = int(threadIdx.x); b < PT_BINS; b += int(blockDim.x))
         if (lh[b] != 0u) atomicAdd(&hist[b], lh[b]);
-}
-// local pixel slot -> image coordinates (cyclic tile ownership, as pt_wave.h)
-__device__ __forceinline__ void pixel_of(int rank, int nranks, int tiles_x, uint32_t pl, int &x, int &y) {
-    const int k = int(pl >> 6), p = int(pl & 63u);
-    const int g = rank + k * nranks;
-    x = (g % tiles_x) * PT_TILE + (p & 7);
-    y = (g / tiles_x) * PT_TILE + (p >> 3);
-}
-__device__ __forceinline__ void pixel_of(const PtLaunch &L, uint32_t pl, int &x, int &y) {
-    pixel_of(L.rank, L.nranks, L.tiles_x, pl, x, y);
 }
 // The first pass's position p -> its sample (frame f, local pixel pl), frame
 // fastest: a 64-ray window is one pixel's camera rays of 64 frames (with 64
@@ -558,7 +545,7 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
             // (the taps' counters go to their own half of the stats buffer:
             // pt_dispatch_stats sums both, bench.py splits the flops by pass)
             // the ray's check[] bits 0..63 (q3.xy) and 64..127 (hi)
-            Check ck{rec_check_lo(q3), uint64_t(hi.x) | (uint64_t(hi.y) << 32)};
+            Check ck{rec_check_lo(q3), check_half(hi.x, hi.y)};
             const float bnd = hq_tap_bound(hq);
             // bnd widened by the taps' spread (two taps are at most 2e apart,
             // plus their coordinates' rounding): the first tap's tests against
@@ -575,14 +562,7 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
                 const Hit h = k == 0 ? Map::template first<ST>(L, qx, qy, qz, ck, bnd, bndw, live, stt)
                                      : Map::template rest<ST>(L, qx, qy, qz, ck, bnd, bndw, live, stt);
                 if (k == 0) ck.alo = Map::alive(live);  // (the other taps' wave-level live test)
-                if ((k & 1) == 0) {
-                    dp = h.d;  // d(p + e)
-                } else {
-                    const float dd = dp - h.d;
-                    if (k == 1) dv0 = dd;
-                    else if (k == 3) dv1 = dd;
-                    else dv2 = dd;
-                }
+                normal_tap(k, h.d, dp, dv0, dv1, dv2);
             }
             stt.add(PT_ST_NORMAL_MAPS, 6);
         }
@@ -946,7 +926,7 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
         ck.alo = wave_or_u64((mapping_now ? ck.lo : 0ull) |
                              (in_win ? rec_check_lo(s3) : 0ull));
         ck.ahi = wide_of<Map>(P) ? wave_or_u64((mapping_now ? ck.hi : 0ull) |
-                                      (in_win ? (uint64_t(sh.x) | (uint64_t(sh.y) << 32)) : 0ull))
+                                      (in_win ? check_half(sh.x, sh.y) : 0ull))
                         : 0ull;
         W[0][lane] = quad_as_uint4(s0);
         W[1][lane] = quad_as_uint4(s1);
@@ -1000,7 +980,7 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
                 if constexpr (MapWide<Map>::v != 0) {
                     if (wide_of<Map>(P)) {
                         const uint4 we = W[4][src];
-                        ck.hi = uint64_t(we.x) | (uint64_t(we.y) << 32);
+                        ck.hi = check_half(we.x, we.y);
                     }
                 }
                 pos = wbase + uint32_t(src);
@@ -1026,8 +1006,7 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
             if (mapping) {
                 float qx, qy, qz;
                 map_point(TAPS ? state : int(ST_MARCH), step, ro, rd, t, qx, qy, qz);
-                uint64_t live = 0;  // (the taps' live mask: unused here)
-                const Hit h = Map::template eval<ST>(L, qx, qy, qz, ck, __builtin_inff(), __builtin_inff(), live, st);
+                const Hit h = map_plain<Map, ST>(L, qx, qy, qz, ck, st);
                 after_map<ST, !TAPS>(h, state, step, t, ro, rd, mat, dv0, dv1, dv2, st);
                 if constexpr (!TAPS) {
                     if (state == ST_NORMAL) {  // hit: the shade pass takes the taps
@@ -1069,21 +1048,16 @@ __device__ __forceinline__ void bin_fold_body(const PtPass &P) {
         pixel_of(L, pl, x, y);
         mine = x < L.width && y < L.height;
     }
-    float4 *texel = mine ? reinterpret_cast<float4 *>(L.accum + (size_t(y) * size_t(L.width) + size_t(x)) * 4) : nullptr;
+    float4 *texel = mine ? accum_texel(L, x, y) : nullptr;
     if (L.debug != 0) {  // direct store of the chunk's (single) frame: one pipeline, one frame
         if (mine) {
             const float4 c = P.color[pl];
-            *texel = make_float4(c.x, c.y, c.z, 1.0f);
+            accum_store(texel, c.x, c.y, c.z);
         }
         return;
     }
     float ar = 0.0f, ag = 0.0f, ab = 0.0f;
-    if (mine) {
-        const float4 v = *texel;
-        ar = v.x;
-        ag = v.y;
-        ab = v.z;
-    }
+    if (mine) accum_load(texel, ar, ag, ab);  // (mine holds L.write; the debug views have returned)
     uint32_t f0 = 0u;  // the chunk frame of region j's first frame
     for (uint32_t j = 0u; j < nl; ++j) {
         const uint32_t fl = fr / nl + (j < fr % nl ? 1u : 0u);
@@ -1106,7 +1080,7 @@ __device__ __forceinline__ void bin_fold_body(const PtPass &P) {
         }
         f0 += fl;
     }
-    if (mine) *texel = make_float4(ar, ag, ab, 1.0f);
+    if (mine) accum_store(texel, ar, ag, ab);
 }
 
 }  // namespace pt

@@ -51,6 +51,17 @@ __device__ __forceinline__ bool lane_check(uint64_t m, int k) {
 __device__ __forceinline__ bool check_bit(const Check &c, int k) {
     return k < 64 ? ((c.lo >> k) & 1ull) != 0 : ((c.hi >> (k - 64)) & 1ull) != 0;
 }
+// check[] entry k (a box's PtAabb.back) set: in a Check, or in the four 32-bit
+// mask words the passes carry it in (word k >> 5, bit k & 31); and two such
+// words joined into a Check half
+__device__ __forceinline__ void check_set(Check &c, int k) {
+    if (k < 64) c.lo |= 1ull << k;
+    else c.hi |= 1ull << (k - 64);
+}
+__device__ __forceinline__ int check_word(int k) { return k >> 5; }
+__device__ __forceinline__ uint32_t check_word_bit(int k) { return 1u << (k & 31); }
+__device__ __forceinline__ void check_set(uint32_t (&w)[4], int k) { w[check_word(k)] |= check_word_bit(k); }
+__device__ __forceinline__ uint64_t check_half(uint32_t lo, uint32_t hi) { return uint64_t(lo) | (uint64_t(hi) << 32); }
 
 template <bool ST>
 struct Stats {
@@ -374,6 +385,14 @@ struct InterpMap {
         return cur;
     }
 };
+
+// The plain map() call of a map type: no distance bound and no live mask
+// (those are the shade pass's taps').
+template <class Map, bool ST>
+__device__ __forceinline__ Hit map_plain(const PtLaunch &L, float x, float y, float z, const Check &ck, Stats<ST> &st) {
+    uint64_t live = 0;  // (the taps' live mask: unused here)
+    return Map::template eval<ST>(L, x, y, z, ck, __builtin_inff(), __builtin_inff(), live, st);
+}
 
 // (base: PT_ST_COUNT for the second half, the shade pass's normal taps)
 template <bool ST>

@@ -17,7 +17,7 @@
 //   mesh_vertex_kernel    one thread per vertex, in full waves: crossing mean, projection, normal, shape
 // No workgroup waits on another: stage boundaries are launch boundaries.  map()
 // is the op-list interpreter (InterpMap) in every kernel.
-#include "pt_common.h"
+#include "pt_path.h"
 #include "pt_mesh.h"
 
 namespace pt {
@@ -34,27 +34,15 @@ __device__ __noinline__ Hit mesh_map(const PtNode *nodes, int32_t n_nodes, float
     L.n_nodes = n_nodes;
     const Check all{~0ull, ~0ull};
     Stats<false> st;
-    uint64_t live = 0;
-    return InterpMap::eval<false>(L, x, y, z, all, __builtin_inff(), __builtin_inff(), live, st);
+    return map_plain<InterpMap, false>(L, x, y, z, all, st);
 }
 
-// calc_normal (pt_kernel.hip; funcs.glsl:21-35) over mesh_map: the six taps
-// +x, -x, +y, -y, +z, -z at e = 1e-4, normalised
+// calc_normal (pt_path.h; funcs.glsl:21-35) over mesh_map, normalised
+__device__ __forceinline__ float mesh_dist(float x, float y, float z, const PtNode *nodes, int32_t n_nodes) {
+    return mesh_map(nodes, n_nodes, x, y, z).d;
+}
 __device__ pt_f3 mesh_normal(const PtNode *nodes, int32_t n_nodes, pt_f3 p) {
-    const float e = 0.0001f;
-    float dv[3];
-    float dplus = 0.0f;
-#pragma unroll 1
-    for (int k = 0; k < 6; ++k) {
-        const int axis = k >> 1;
-        const bool neg = (k & 1) != 0;
-        const float on = neg ? -e : e, off = neg ? -0.0f : 0.0f;
-        const float d = mesh_map(nodes, n_nodes, p.x + (axis == 0 ? on : off), p.y + (axis == 1 ? on : off),
-                                 p.z + (axis == 2 ? on : off)).d;
-        if (!neg) dplus = d;
-        else dv[axis] = dplus - d;
-    }
-    return pt_normalize(pt_f3{dv[0], dv[1], dv[2]});
+    return pt_normalize(calc_normal<mesh_dist>(p, nodes, n_nodes));
 }
 
 __global__ __launch_bounds__(256) void mesh_sample_kernel(PtMeshScene S, const float *__restrict__ xyz, uint32_t n,

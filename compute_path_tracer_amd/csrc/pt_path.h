@@ -116,15 +116,34 @@ __device__ __forceinline__ void sky_miss(const PtLaunch &L, const pt_f3 &rd, con
     ret.z = ret.z + g.z * thr.z;
 }
 
-// bounds(): one box's slab test, intersectAABB + bool_hit (aabb.glsl:21-33),
-// as the generated bounds() applies it per check[] entry.
+// The slab test's tail, intersectAABB + bool_hit (aabb.glsl:21-33), stated
+// once for the five forms below: the ray's parameter range inside the three
+// slabs from the six slab values, and the hit test on it.  DESIGN.md 3.14,
+// 3.18 and 3.19 argue about these two functions.
+__device__ __forceinline__ void slab_ends(float tminx, float tmaxx, float tminy, float tmaxy, float tminz, float tmaxz,
+                                          float &tnear, float &tfar) {
+    tnear = pt_gmax(pt_gmax(pt_gmin(tminx, tmaxx), pt_gmin(tminy, tmaxy)), pt_gmin(tminz, tmaxz));
+    tfar = pt_gmin(pt_gmin(pt_gmax(tminx, tmaxx), pt_gmax(tminy, tmaxy)), pt_gmax(tminz, tmaxz));
+}
+__device__ __forceinline__ bool slab_hit(float tnear, float tfar) { return tnear < tfar && tfar > 0.0f; }
+
+// The ray inside the reciprocal guard (pt_math.h pt_div_*_ok): with the
+// scene's boxes inside it too (L.fast_bounds), bounds() may take its slab
+// values from per-ray reciprocals.  The fast path of bounds_mask, the box skip
+// (pt_binned.h; 3.20's proof needs the two to agree) and the self-test use
+// this one; the generated bounds() keeps its own `&` form of the same six
+// tests (pt_jit.cpp emit_map_bounds).
+__device__ __forceinline__ bool ray_in_guard(const pt_f3 &ro, const pt_f3 &rd) {
+    return pt_div_coord_ok(ro.x) && pt_div_coord_ok(ro.y) && pt_div_coord_ok(ro.z) && pt_div_dir_ok(rd.x) &&
+           pt_div_dir_ok(rd.y) && pt_div_dir_ok(rd.z);
+}
+
+// bounds(): one box's slab test as the generated bounds() applies it per check[] entry.
 __device__ __forceinline__ bool ray_box(const PtAabb &bx, float ox, float oy, float oz, float dx, float dy, float dz) {
-    const float tminx = (bx.bmin[0] - ox) / dx, tmaxx = (bx.bmax[0] - ox) / dx;
-    const float tminy = (bx.bmin[1] - oy) / dy, tmaxy = (bx.bmax[1] - oy) / dy;
-    const float tminz = (bx.bmin[2] - oz) / dz, tmaxz = (bx.bmax[2] - oz) / dz;
-    const float tnear = pt_gmax(pt_gmax(pt_gmin(tminx, tmaxx), pt_gmin(tminy, tmaxy)), pt_gmin(tminz, tmaxz));
-    const float tfar = pt_gmin(pt_gmin(pt_gmax(tminx, tmaxx), pt_gmax(tminy, tmaxy)), pt_gmax(tminz, tmaxz));
-    return tnear < tfar && tfar > 0.0f;
+    float tnear, tfar;
+    slab_ends((bx.bmin[0] - ox) / dx, (bx.bmax[0] - ox) / dx, (bx.bmin[1] - oy) / dy, (bx.bmax[1] - oy) / dy,
+              (bx.bmin[2] - oz) / dz, (bx.bmax[2] - oz) / dz, tnear, tfar);
+    return slab_hit(tnear, tfar);
 }
 
 // The same test with the divisions as pt_div_rcp from per-ray reciprocals
@@ -132,16 +151,22 @@ __device__ __forceinline__ bool ray_box(const PtAabb &bx, float ox, float oy, fl
 // the ray and the box (bounds_mask in pt_binned.h).
 __device__ __forceinline__ bool ray_box_rcp(const PtAabb &bx, float ox, float oy, float oz, float dx, float dy,
                                             float dz, float yx, float yy, float yz) {
-    const float tminx = pt_div_rcp(bx.bmin[0] - ox, dx, yx), tmaxx = pt_div_rcp(bx.bmax[0] - ox, dx, yx);
-    const float tminy = pt_div_rcp(bx.bmin[1] - oy, dy, yy), tmaxy = pt_div_rcp(bx.bmax[1] - oy, dy, yy);
-    const float tminz = pt_div_rcp(bx.bmin[2] - oz, dz, yz), tmaxz = pt_div_rcp(bx.bmax[2] - oz, dz, yz);
-    const float tnear = pt_gmax(pt_gmax(pt_gmin(tminx, tmaxx), pt_gmin(tminy, tmaxy)), pt_gmin(tminz, tmaxz));
-    const float tfar = pt_gmin(pt_gmin(pt_gmax(tminx, tmaxx), pt_gmax(tminy, tmaxy)), pt_gmax(tminz, tmaxz));
-    return tnear < tfar && tfar > 0.0f;
+    float tnear, tfar;
+    slab_ends(pt_div_rcp(bx.bmin[0] - ox, dx, yx), pt_div_rcp(bx.bmax[0] - ox, dx, yx),
+              pt_div_rcp(bx.bmin[1] - oy, dy, yy), pt_div_rcp(bx.bmax[1] - oy, dy, yy),
+              pt_div_rcp(bx.bmin[2] - oz, dz, yz), pt_div_rcp(bx.bmax[2] - oz, dz, yz), tnear, tfar);
+    return slab_hit(tnear, tfar);
 }
 
-// The slab test from the reciprocal products alone: t' = RN(a * y) with a =
-// RN(bmin - o) as in ray_box_rcp and y = RN(1/d).  Under the same guards,
+// The slab ends from the reciprocal products alone: t' = RN(a * y) with a =
+// RN(bmin - o) as in ray_box_rcp and y = RN(1/d) (ray_box_approx, ray_box_ulp).
+__device__ __forceinline__ void slab_ends_rcp(const PtAabb &bx, float ox, float oy, float oz, float yx, float yy,
+                                              float yz, float &tnear, float &tfar) {
+    slab_ends((bx.bmin[0] - ox) * yx, (bx.bmax[0] - ox) * yx, (bx.bmin[1] - oy) * yy, (bx.bmax[1] - oy) * yy,
+              (bx.bmin[2] - oz) * yz, (bx.bmax[2] - oz) * yz, tnear, tfar);
+}
+
+// The slab test from those products.  Under the same guards,
 // |t' - t| <= 3 * 2^-24 |t| for every slab value t = RN(a / d), and t' has
 // t's sign and zeros, so:
 //  * tfar' > 0 exactly when tfar > 0 (min / max keep the signs);
@@ -151,13 +176,10 @@ __device__ __forceinline__ bool ray_box_rcp(const PtAabb &bx, float ox, float oy
 //    boxes tested, and a lane whose gap is <= 0 takes ray_box_rcp.
 __device__ __forceinline__ bool ray_box_approx(const PtAabb &bx, float ox, float oy, float oz, float yx, float yy,
                                                float yz, float &gap) {
-    const float tminx = (bx.bmin[0] - ox) * yx, tmaxx = (bx.bmax[0] - ox) * yx;
-    const float tminy = (bx.bmin[1] - oy) * yy, tmaxy = (bx.bmax[1] - oy) * yy;
-    const float tminz = (bx.bmin[2] - oz) * yz, tmaxz = (bx.bmax[2] - oz) * yz;
-    const float tnear = pt_gmax(pt_gmax(pt_gmin(tminx, tmaxx), pt_gmin(tminy, tmaxy)), pt_gmin(tminz, tmaxz));
-    const float tfar = pt_gmin(pt_gmin(pt_gmax(tminx, tmaxx), pt_gmax(tminy, tmaxy)), pt_gmax(tminz, tmaxz));
+    float tnear, tfar;
+    slab_ends_rcp(bx, ox, oy, oz, yx, yy, yz, tnear, tfar);
     gap = fminf(gap, fabsf(tfar - tnear) - (fabsf(tnear) + fabsf(tfar)) * 0x1p-20f);
-    return tnear < tfar && tfar > 0.0f;
+    return slab_hit(tnear, tfar);
 }
 
 // ray_box_approx with the margin in units of the last place (DESIGN.md
@@ -182,13 +204,10 @@ __device__ __forceinline__ uint32_t pt_absdiff_u32(uint32_t a, uint32_t b) {
 template <bool SAD = true>
 __device__ __forceinline__ bool ray_box_ulp(const PtAabb &bx, float ox, float oy, float oz, float yx, float yy,
                                             float yz, uint32_t &gapu) {
-    const float tminx = (bx.bmin[0] - ox) * yx, tmaxx = (bx.bmax[0] - ox) * yx;
-    const float tminy = (bx.bmin[1] - oy) * yy, tmaxy = (bx.bmax[1] - oy) * yy;
-    const float tminz = (bx.bmin[2] - oz) * yz, tmaxz = (bx.bmax[2] - oz) * yz;
-    const float tnear = pt_gmax(pt_gmax(pt_gmin(tminx, tmaxx), pt_gmin(tminy, tmaxy)), pt_gmin(tminz, tmaxz));
-    const float tfar = pt_gmin(pt_gmin(pt_gmax(tminx, tmaxx), pt_gmax(tminy, tmaxy)), pt_gmax(tminz, tmaxz));
+    float tnear, tfar;
+    slab_ends_rcp(bx, ox, oy, oz, yx, yy, yz, tnear, tfar);
     gapu = min(gapu, pt_absdiff_u32<SAD>(__float_as_uint(tfar), __float_as_uint(tnear)));
-    return tnear < tfar && tfar > 0.0f;
+    return slab_hit(tnear, tfar);
 }
 
 // The slab test from one fma per slab: t' = RN(b * y + n) with n = -RN(o * y)
@@ -201,14 +220,12 @@ __device__ __forceinline__ bool ray_box_ulp(const PtAabb &bx, float ox, float oy
 // subtraction and a product.
 __device__ __forceinline__ bool ray_box_fma(const PtAabb &bx, float nx, float ny, float nz, float yx, float yy,
                                             float yz, float &gap, float &tfa) {
-    const float tminx = fmaf(bx.bmin[0], yx, nx), tmaxx = fmaf(bx.bmax[0], yx, nx);
-    const float tminy = fmaf(bx.bmin[1], yy, ny), tmaxy = fmaf(bx.bmax[1], yy, ny);
-    const float tminz = fmaf(bx.bmin[2], yz, nz), tmaxz = fmaf(bx.bmax[2], yz, nz);
-    const float tnear = pt_gmax(pt_gmax(pt_gmin(tminx, tmaxx), pt_gmin(tminy, tmaxy)), pt_gmin(tminz, tmaxz));
-    const float tfar = pt_gmin(pt_gmin(pt_gmax(tminx, tmaxx), pt_gmax(tminy, tmaxy)), pt_gmax(tminz, tmaxz));
+    float tnear, tfar;
+    slab_ends(fmaf(bx.bmin[0], yx, nx), fmaf(bx.bmax[0], yx, nx), fmaf(bx.bmin[1], yy, ny), fmaf(bx.bmax[1], yy, ny),
+              fmaf(bx.bmin[2], yz, nz), fmaf(bx.bmax[2], yz, nz), tnear, tfar);
     gap = fminf(gap, fabsf(tfar - tnear) - (fabsf(tnear) + fabsf(tfar)) * 0x1p-20f);
     tfa = fminf(tfa, fabsf(tfar));
-    return tnear < tfar && tfar > 0.0f;
+    return slab_hit(tnear, tfar);
 }
 __device__ __forceinline__ bool fma_decided(float gap, float tfa, float nx, float ny, float nz) {
     const float m = pt_gmax(fabsf(nx), pt_gmax(fabsf(ny), fabsf(nz)));
@@ -233,6 +250,39 @@ __device__ __forceinline__ void map_point(int state, int step, const pt_f3 &ro, 
         qy = ro.y + (axis == 1 ? on : off);
         qz = ro.z + (axis == 2 ? on : off);
     }
+}
+
+// calc_normal's bookkeeping for tap k with map() value d: an even tap keeps
+// d(p + e) in dplus, an odd one stores d(p + e) - d(p - e) for its axis.
+__device__ __forceinline__ void normal_tap(int k, float d, float &dplus, float &dv0, float &dv1, float &dv2) {
+    if ((k & 1) == 0) {
+        dplus = d;
+    } else {
+        const float dd = dplus - d;
+        if (k == 1) dv0 = dd;
+        else if (k == 3) dv1 = dd;
+        else dv2 = dd;
+    }
+}
+
+// calc_normal (funcs.glsl:21-35): central differences, e = 1e-4, over
+// map_point's six taps (the zero components of -e are -0.0, so p.y + (-0.0)
+// == p.y exactly); MapAt(x, y, z, args...) is the map() distance at a point (a
+// function, not a closure: with a closure in an out-of-line caller the simple
+// kernel copies its launch block to scratch).  The caller normalises.
+template <auto MapAt, class... Args>
+__device__ __forceinline__ pt_f3 calc_normal(const pt_f3 &p, Args &&...args) {
+    float dv[3], dplus = 0.0f;
+#pragma unroll 1
+    for (int k = 0; k < 6; ++k) {
+        float qx, qy, qz;
+        map_point(ST_NORMAL, k, p, p, 0.0f, qx, qy, qz);
+        const float d = MapAt(qx, qy, qz, args...);
+        // (normal_tap written out on an array: through it mesh_vertex_kernel gains 28 instructions, 0.665 -> 0.667 ms)
+        if ((k & 1) == 0) dplus = d;
+        else dv[k >> 1] = dplus - d;
+    }
+    return pt_f3{dv[0], dv[1], dv[2]};
 }
 
 // Advance a MARCH / NORMAL lane by the map() result h.  MARCH: CastRay's loop
@@ -260,14 +310,7 @@ __device__ __forceinline__ void after_map(const Hit &h, int &state, int &step, f
             }
         }
     } else if constexpr (!MARCH_ONLY) {
-        if ((step & 1) == 0) {
-            t = h.d;  // d(p + e)
-        } else {
-            const float dd = t - h.d;
-            if (step == 1) dv0 = dd;
-            else if (step == 3) dv1 = dd;
-            else dv2 = dd;
-        }
+        normal_tap(step, h.d, t, dv0, dv1, dv2);  // (t keeps d(p + e))
         ++step;
         if (step == 6) {
             st.add(PT_ST_NORMAL_MAPS, 6);
@@ -362,5 +405,45 @@ __device__ __forceinline__ void mix_frame(float &ar, float &ag, float &ab, const
     ag = ag * omw + colour.y * w;
     ab = ab * omw + colour.z * w;
 }
+
+// Tile to pixel.  Ranks own the 8x8 tiles cyclically: a rank's local tile k is
+// tile g = rank + k * nranks of the image, row-major; lane p of a tile is pixel
+// (p & 7, p >> 3) from its origin.  pixel_of: local pixel slot pl = k * 64 + p.
+// (One function per term: pixel_of over a two-step origin / offset pair
+// reordered instructions of the scene kernels' gen pass.)
+__device__ __forceinline__ int tile_index(int rank, int nranks, int k) { return rank + k * nranks; }
+__device__ __forceinline__ int tile_x0(int g, int tiles_x) { return (g % tiles_x) * PT_TILE; }
+__device__ __forceinline__ int tile_y0(int g, int tiles_x) { return (g / tiles_x) * PT_TILE; }
+__device__ __forceinline__ int lane_dx(int p) { return p & 7; }
+__device__ __forceinline__ int lane_dy(int p) { return p >> 3; }
+__device__ __forceinline__ void pixel_of(int rank, int nranks, int tiles_x, uint32_t pl, int &x, int &y) {
+    const int k = int(pl >> 6), p = int(pl & 63u);
+    const int g = tile_index(rank, nranks, k);
+    x = tile_x0(g, tiles_x) + lane_dx(p);
+    y = tile_y0(g, tiles_x) + lane_dy(p);
+}
+__device__ __forceinline__ void pixel_of(const PtLaunch &L, uint32_t pl, int &x, int &y) {
+    pixel_of(L.rank, L.nranks, L.tiles_x, pl, x, y);
+}
+
+// The accumulation texel of pixel (x, y) over a launch: its address, its
+// running colour, and the (r, g, b, 1) store.  accum_mixes: the launch starts
+// from the texel's colour only when it mixes frames into it -- a debug view
+// stores its last frame, and write = 0 leaves the image alone.  first_frame: a
+// debug view renders only the launch's last frame, the one its store keeps.
+__device__ __forceinline__ float4 *accum_texel(const PtLaunch &L, int x, int y) {
+    return reinterpret_cast<float4 *>(L.accum + (size_t(y) * size_t(L.width) + size_t(x)) * 4);
+}
+__device__ __forceinline__ bool accum_mixes(const PtLaunch &L) { return L.debug == 0 && L.write; }
+__device__ __forceinline__ void accum_load(const float4 *texel, float &ar, float &ag, float &ab) {
+    const float4 v = *texel;
+    ar = v.x;
+    ag = v.y;
+    ab = v.z;
+}
+__device__ __forceinline__ void accum_store(float4 *texel, float ar, float ag, float ab) {
+    *texel = make_float4(ar, ag, ab, 1.0f);
+}
+__device__ __forceinline__ int first_frame(const PtLaunch &L) { return L.debug != 0 ? L.spp - 1 : 0; }
 
 }  // namespace pt

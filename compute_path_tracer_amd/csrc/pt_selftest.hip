@@ -159,10 +159,8 @@ __global__ void box_random(uint32_t seed, uint32_t n, int mode, unsigned long lo
         if (d[a2] > 0.0f) b.bmax[a2] = __uint_as_float(__float_as_uint(p[a2]) + uint32_t(u2));
         else b.bmin[a2] = __uint_as_float(__float_as_uint(p[a2]) + uint32_t(u2));
     }
-    bool ok = true;
-    for (int k = 0; k < 3; ++k)
-        ok = ok && pt_div_coord_ok(o[k]) && pt_div_dir_ok(d[k]) && pt_div_coord_ok(b.bmin[k]) &&
-             pt_div_coord_ok(b.bmax[k]);
+    bool ok = pt::ray_in_guard(pt_f3{o[0], o[1], o[2]}, pt_f3{d[0], d[1], d[2]});
+    for (int k = 0; k < 3; ++k) ok = ok && pt_div_coord_ok(b.bmin[k]) && pt_div_coord_ok(b.bmax[k]);
     if (!ok) {
         atomicAdd(cnt + 3, 1ull);
         return;
@@ -209,87 +207,70 @@ __global__ void divk_sweep(uint32_t a0, float b, unsigned long long *bad, unsign
     }
 }
 
+typedef unsigned long long Word;
+// One self-test run on a device: N counter words there holding `init`, then
+// `launches` kernel launches (launch(d, k), k = 0.., each waited for; the first
+// failure ends the run), the words copied back and handed to done(h), the
+// buffer freed.  done() runs once the buffer exists, whatever failed after
+// (it then sees zeros).
+template <size_t N, class Launch, class Done>
+int run_counted(int hip_device, const Word (&init)[N], uint64_t launches, Launch launch, Done done) {
+    if (hipSetDevice(hip_device) != hipSuccess) return PT_ERR_HIP;
+    Word *d = nullptr;
+    if (hipMalloc(&d, sizeof init) != hipSuccess) return PT_ERR_HIP;
+    int rc = hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice) == hipSuccess ? PT_OK : PT_ERR_HIP;
+    for (uint64_t k = 0; rc == PT_OK && k < launches; ++k) {
+        launch(d, k);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = PT_ERR_HIP;
+    }
+    Word h[N] = {};
+    if (rc == PT_OK && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = PT_ERR_HIP;
+    done(h);
+    (void)hipFree(d);
+    return rc;
+}
+const Word kCountAndFirst[2] = {0ull, ~0ull};  // mismatches, the least bad operand
+template <class First>
+auto count_and_first(uint64_t *count, First *first) {  // done() of the runs that report those two
+    return [=](const Word *h) { *count = h[0], *first = First(h[1]); };
+}
+
 }  // namespace
 
 extern "C" int pt_check_div_k(int hip_device, float b, uint32_t a0, uint32_t na, uint64_t *mismatches,
                               uint64_t *first_bad) {
     if (!mismatches || !first_bad || na % 256u != 0u || a0 + uint64_t(na) > (1ull << 32)) return PT_ERR_INVALID;
-    if (hipSetDevice(hip_device) != hipSuccess) return PT_ERR_HIP;
-    unsigned long long *d = nullptr;
-    if (hipMalloc(&d, 2 * sizeof(*d)) != hipSuccess) return PT_ERR_HIP;
-    const unsigned long long init[2] = {0ull, ~0ull};
-    int rc = hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice) == hipSuccess ? PT_OK : PT_ERR_HIP;
-    for (uint64_t a = a0; rc == PT_OK && a < uint64_t(a0) + na; a += 1ull << 28) {  // 2^28 per launch
-        const uint64_t cnt = std::min<uint64_t>(1ull << 28, uint64_t(a0) + na - a);
+    return run_counted(hip_device, kCountAndFirst, (uint64_t(na) + (1ull << 28) - 1) >> 28, [&](Word *d, uint64_t k) {
+        const uint64_t a = a0 + (k << 28), cnt = std::min<uint64_t>(1ull << 28, uint64_t(a0) + na - a);  // 2^28 per launch
         hipLaunchKernelGGL(divk_sweep, dim3(unsigned(cnt / 256u)), dim3(256), 0, 0, uint32_t(a), b, d, d + 1);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = PT_ERR_HIP;
-    }
-    unsigned long long h[2] = {0ull, 0ull};
-    if (rc == PT_OK && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = PT_ERR_HIP;
-    *mismatches = h[0];
-    *first_bad = h[1];
-    (void)hipFree(d);
-    return rc;
+    }, count_and_first(mismatches, first_bad));
 }
 
 extern "C" int pt_check_box_random(int hip_device, uint32_t seed, uint32_t n, int mode, uint64_t *counts) {
     if (!counts) return PT_ERR_INVALID;
-    if (hipSetDevice(hip_device) != hipSuccess) return PT_ERR_HIP;
-    unsigned long long *d = nullptr;
-    if (hipMalloc(&d, 4 * sizeof(*d)) != hipSuccess) return PT_ERR_HIP;
-    int rc = hipMemset(d, 0, 4 * sizeof(*d)) == hipSuccess ? PT_OK : PT_ERR_HIP;
-    if (rc == PT_OK && n > 0) {
+    const Word zero[4] = {0ull, 0ull, 0ull, 0ull};
+    return run_counted(hip_device, zero, n > 0 ? 1 : 0, [&](Word *d, uint64_t) {
         hipLaunchKernelGGL(box_random, dim3((n + 255) / 256), dim3(256), 0, 0, seed, n, mode, d);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = PT_ERR_HIP;
-    }
-    unsigned long long h[4] = {0ull, 0ull, 0ull, 0ull};
-    if (rc == PT_OK && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = PT_ERR_HIP;
-    for (int k = 0; k < 4; ++k) counts[k] = h[k];
-    (void)hipFree(d);
-    return rc;
+    }, [&](const Word *h) { std::copy(h, h + 4, counts); });
 }
 
 extern "C" int pt_check_div_exhaustive(int hip_device, uint32_t a0, uint32_t na, uint32_t b0, uint32_t nb,
                                        uint64_t *mismatches, uint64_t *first_bad) {
     if (!mismatches || !first_bad || a0 + uint64_t(na) > (1u << 23) || b0 + uint64_t(nb) > (1u << 23))
         return PT_ERR_INVALID;
-    if (hipSetDevice(hip_device) != hipSuccess) return PT_ERR_HIP;
-    unsigned long long *d = nullptr;
-    if (hipMalloc(&d, 2 * sizeof(*d)) != hipSuccess) return PT_ERR_HIP;
-    const unsigned long long init[2] = {0ull, ~0ull};
-    int rc = hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice) == hipSuccess ? PT_OK : PT_ERR_HIP;
     // slices of a keep each launch well under a second
-    for (uint32_t a = a0; rc == PT_OK && a < a0 + na; a += 1u << 15) {
-        const uint32_t cnt = std::min<uint32_t>(1u << 15, a0 + na - a);
+    return run_counted(hip_device, kCountAndFirst, (uint64_t(na) + (1u << 15) - 1) >> 15, [&](Word *d, uint64_t k) {
+        const uint32_t a = a0 + (uint32_t(k) << 15), cnt = std::min<uint32_t>(1u << 15, a0 + na - a);
         hipLaunchKernelGGL(div_sweep, dim3((nb + 255) / 256), dim3(256), 0, 0, a, cnt, b0, nb, d, d + 1);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = PT_ERR_HIP;
-    }
-    unsigned long long h[2] = {0ull, 0ull};
-    if (rc == PT_OK && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = PT_ERR_HIP;
-    *mismatches = h[0];
-    *first_bad = h[1];
-    (void)hipFree(d);
-    return rc;
+    }, count_and_first(mismatches, first_bad));
 }
 
 extern "C" int pt_check_div_random(int hip_device, uint32_t seed, uint32_t n, uint64_t *mismatches,
                                    uint64_t *first_bad) {
     if (!mismatches || !first_bad) return PT_ERR_INVALID;
-    if (hipSetDevice(hip_device) != hipSuccess) return PT_ERR_HIP;
-    unsigned long long *d = nullptr;
-    if (hipMalloc(&d, 2 * sizeof(*d)) != hipSuccess) return PT_ERR_HIP;
-    const unsigned long long init[2] = {0ull, ~0ull};
-    int rc = hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice) == hipSuccess ? PT_OK : PT_ERR_HIP;
-    if (rc == PT_OK && n > 0) {
+    return run_counted(hip_device, kCountAndFirst, n > 0 ? 1 : 0, [&](Word *d, uint64_t) {
         hipLaunchKernelGGL(div_random, dim3((n + 255) / 256), dim3(256), 0, 0, seed, n, d, d + 1);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = PT_ERR_HIP;
-    }
-    unsigned long long h[2] = {0ull, 0ull};
-    if (rc == PT_OK && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = PT_ERR_HIP;
-    *mismatches = h[0];
-    *first_bad = h[1];
-    (void)hipFree(d);
-    return rc;
+    }, count_and_first(mismatches, first_bad));
 }
 
 extern "C" int pt_device_math(int hip_device, int op, const float *a, const float *b, float *out, uint32_t n) {
@@ -319,29 +300,9 @@ extern "C" int pt_device_math(int hip_device, int op, const float *a, const floa
 
 extern "C" int pt_check_sqrt_exhaustive(int hip_device, uint64_t *mismatches, uint32_t *first_bad) {
     if (!mismatches || !first_bad) return PT_ERR_INVALID;
-    if (hipSetDevice(hip_device) != hipSuccess) return PT_ERR_HIP;
-    unsigned long long *dbad = nullptr;
-    uint32_t *dfirst = nullptr;
-    if (hipMalloc(&dbad, sizeof(*dbad)) != hipSuccess || hipMalloc(&dfirst, sizeof(*dfirst)) != hipSuccess)
-        return PT_ERR_HIP;
-    const uint32_t init_first = 0xffffffffu;
-    int rc = PT_OK;
-    if (hipMemset(dbad, 0, sizeof(*dbad)) != hipSuccess ||
-        hipMemcpy(dfirst, &init_first, sizeof(init_first), hipMemcpyHostToDevice) != hipSuccess)
-        rc = PT_ERR_HIP;
-    // 2^32 inputs in 4 chunks of 2^30
-    for (uint64_t base = 0; rc == PT_OK && base < (1ull << 32); base += (1ull << 30)) {
-        hipLaunchKernelGGL(sqrt_sweep, dim3(8192), dim3(256), 0, 0, base, uint32_t(1u << 30), dbad, dfirst);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = PT_ERR_HIP;
-    }
-    unsigned long long hb = 0;
-    uint32_t hf = 0;
-    if (rc == PT_OK && (hipMemcpy(&hb, dbad, sizeof(hb), hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(&hf, dfirst, sizeof(hf), hipMemcpyDeviceToHost) != hipSuccess))
-        rc = PT_ERR_HIP;
-    *mismatches = hb;
-    *first_bad = hf;
-    (void)hipFree(dbad);
-    (void)hipFree(dfirst);
-    return rc;
+    const Word init[2] = {0ull, 0xffffffffull};  // (the least bad pattern is 32 bits: the low half of word 1)
+    return run_counted(hip_device, init, 4, [&](Word *d, uint64_t k) {  // 2^32 inputs in 4 chunks of 2^30
+        hipLaunchKernelGGL(sqrt_sweep, dim3(8192), dim3(256), 0, 0, k << 30, uint32_t(1u << 30), d,
+                           reinterpret_cast<uint32_t *>(d + 1));
+    }, count_and_first(mismatches, first_bad));
 }

@@ -25,7 +25,7 @@ def test_tile_spec_covers_every_rank(width, height, world):
 
 
 def test_tile_ids_match_the_kernels_tiling():
-    """pt_binned.h pixel_of: tile g's texels are x in [(g % tx) * 8, +8),
+    """pt_path.h pixel_of: tile g's texels are x in [(g % tx) * 8, +8),
     y in [(g // tx) * 8, +8), ragged at the right and top edges."""
     ids = bench.tile_ids(20, 11)
     tx = 3
