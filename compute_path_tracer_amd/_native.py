@@ -42,17 +42,6 @@ STAT_NAMES = (
 
 PT_ST_COUNT = len(STAT_NAMES)  # device counters (pt_device.h PT_ST_COUNT)
 
-SYMBOLS = (
-    "pt_compile_scene", "pt_create", "pt_resize_clear", "pt_set_program", "pt_set_data", "pt_set_tiles",
-    "pt_dispatch", "pt_read_accum", "pt_accum_device_ptr", "pt_get_size", "pt_comm_get_unique_id",
-    "pt_comm_init", "pt_reduce_accum", "pt_read_reduced", "pt_sync", "pt_last_dispatch_ms",
-    "pt_dispatch_stats", "pt_set_option", "pt_get_option", "pt_jit_log", "pt_jit_compile", "pt_last_error",
-    "pt_destroy", "pt_abi_version", "pt_device_math", "pt_check_sqrt_exhaustive", "pt_check_div_exhaustive",
-    "pt_check_div_random", "pt_check_box_random", "pt_check_div_k", "pt_display", "pt_write_accum",
-    "pt_compile_scene_keyed", "pt_save_rgba8", "pt_comm_size", "pt_traffic_probe", "pt_scene_kernel_source",
-    "pt_set_camera", "pt_get_camera", "pt_set_sky", "pt_get_sky", "pt_render_guides", "pt_read_guides", "pt_denoise",
-    "pt_sample_field", "pt_mesh_extract", "pt_mesh_read",
-)
 PT_MATH = {"max": 0, "min": 1, "sqrt": 2, "sqrtf": 3, "sin": 4, "cos": 5, "div": 6, "fma": 7}
 
 
@@ -149,6 +138,66 @@ assert ctypes.sizeof(MeshDesc) == 36 and ctypes.sizeof(MeshInfo) == 48
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
 
+# Every entry point include/pt_abi.h declares: name -> (restype, argtypes).
+_ctx = c_void_p
+_u32p, _f32p = POINTER(c_uint32), POINTER(c_float)
+SIGNATURES = {
+    "pt_compile_scene": (c_int, [POINTER(SceneNode), c_uint32, POINTER(Op), c_uint32, _u32p, POINTER(Aabb), c_uint32,
+                                 _u32p, _f32p, c_uint32, _u32p, _u32p]),
+    "pt_compile_scene_keyed": (c_int, [POINTER(SceneNode), c_uint32, POINTER(FloatKey), POINTER(Op), c_uint32, _u32p,
+                                       POINTER(Aabb), c_uint32, _u32p, _f32p, c_uint32, _u32p, _u32p]),
+    "pt_save_rgba8": (c_int, [_f32p, c_uint32, c_uint32, POINTER(c_uint8), c_size_t]),
+    "pt_create": (c_int, [c_int, c_uint32, c_uint32, POINTER(_ctx)]),
+    "pt_resize_clear": (c_int, [_ctx, c_uint32, c_uint32]),
+    "pt_set_program": (c_int, [_ctx, POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, c_uint32]),
+    "pt_set_data": (c_int, [_ctx, _f32p, c_uint32]),
+    "pt_set_tiles": (c_int, [_ctx, c_uint32, c_uint32]),
+    "pt_set_camera": (c_int, [_ctx, POINTER(Camera)]),
+    "pt_get_camera": (c_int, [_ctx, POINTER(Camera), POINTER(c_int)]),
+    "pt_set_sky": (c_int, [_ctx, POINTER(Sky)]),
+    "pt_get_sky": (c_int, [_ctx, POINTER(Sky), POINTER(c_int)]),
+    "pt_dispatch": (c_int, [_ctx, POINTER(Constants), POINTER(Settings), c_uint32]),
+    "pt_read_accum": (c_int, [_ctx, _f32p, c_size_t]),
+    "pt_accum_device_ptr": (c_int, [_ctx, POINTER(c_void_p), POINTER(c_size_t)]),
+    "pt_get_size": (c_int, [_ctx, _u32p, _u32p]),
+    "pt_comm_get_unique_id": (c_int, [POINTER(c_uint8)]),
+    "pt_comm_init": (c_int, [_ctx, c_uint32, c_uint32, POINTER(c_uint8)]),
+    "pt_comm_size": (c_int, [_ctx, _u32p]),
+    "pt_reduce_accum": (c_int, [_ctx, c_int]),
+    "pt_read_reduced": (c_int, [_ctx, _f32p, c_size_t]),
+    "pt_sync": (c_int, [_ctx]),
+    "pt_last_dispatch_ms": (c_int, [_ctx, _f32p]),
+    "pt_dispatch_stats": (c_int, [_ctx, POINTER(Constants), POINTER(Settings), c_uint32, POINTER(c_uint64)]),
+    "pt_set_option": (c_int, [_ctx, c_char_p, c_int]),
+    "pt_get_option": (c_int, [_ctx, c_char_p, POINTER(ctypes.c_double)]),
+    "pt_jit_log": (c_char_p, [_ctx]),
+    "pt_jit_compile": (c_int, [POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, _f32p, c_uint32, c_char_p,
+                               c_size_t, POINTER(c_size_t)]),
+    "pt_scene_kernel_source": (c_int, [POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, _f32p, c_uint32,
+                                       c_int, c_char_p, c_size_t, POINTER(c_size_t)]),
+    "pt_last_error": (c_char_p, [_ctx]),
+    "pt_destroy": (None, [_ctx]),
+    "pt_abi_version": (c_int, []),
+    "pt_device_math": (c_int, [c_int, c_int, _f32p, _f32p, _f32p, c_uint32]),
+    "pt_check_sqrt_exhaustive": (c_int, [c_int, POINTER(c_uint64), POINTER(c_uint32)]),
+    "pt_check_div_exhaustive": (c_int, [c_int, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_uint64),
+                                        POINTER(c_uint64)]),
+    "pt_check_div_random": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_uint64), POINTER(c_uint64)]),
+    "pt_check_box_random": (c_int, [c_int, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
+    "pt_check_div_k": (c_int, [c_int, c_float, c_uint32, c_uint32, POINTER(c_uint64), POINTER(c_uint64)]),
+    "pt_traffic_probe": (c_int, [c_int, c_uint32, _f32p, POINTER(c_uint64)]),
+    "pt_display": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "pt_write_accum": (c_int, [c_void_p, _f32p, c_size_t]),
+    "pt_render_guides": (c_int, [_ctx, POINTER(Constants), POINTER(Settings)]),
+    "pt_read_guides": (c_int, [_ctx, _f32p, _f32p, c_size_t]),
+    "pt_denoise": (c_int, [_ctx, POINTER(DenoiseParams), c_int, c_void_p, c_size_t]),
+    "pt_sample_field": (c_int, [_ctx, _f32p, c_uint32, _f32p, POINTER(c_int32)]),
+    "pt_mesh_extract": (c_int, [_ctx, POINTER(MeshDesc), POINTER(MeshInfo)]),
+    "pt_mesh_read": (c_int, [_ctx, _f32p, _f32p, POINTER(c_int32), _u32p, c_size_t, c_size_t]),
+}
+SYMBOLS = tuple(SIGNATURES)
+
+
 class NativeError(RuntimeError):
     def __init__(self, fn: str, code: int, msg: str):
         super().__init__(f"{fn} failed ({code}): {msg}")
@@ -167,63 +216,7 @@ def lib() -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(f"HIP library {path} missing: run __graft_entry__.build() (no CPU fallback exists)")
     L = ctypes.CDLL(path)
-    ctx = c_void_p
-    u32p = POINTER(c_uint32)
-    sig = {
-        "pt_compile_scene": (c_int, [POINTER(SceneNode), c_uint32, POINTER(Op), c_uint32, u32p, POINTER(Aabb), c_uint32,
-                                     u32p, POINTER(c_float), c_uint32, u32p, u32p]),
-        "pt_compile_scene_keyed": (c_int, [POINTER(SceneNode), c_uint32, POINTER(FloatKey), POINTER(Op), c_uint32, u32p,
-                                           POINTER(Aabb), c_uint32, u32p, POINTER(c_float), c_uint32, u32p, u32p]),
-        "pt_save_rgba8": (c_int, [POINTER(c_float), c_uint32, c_uint32, POINTER(c_uint8), c_size_t]),
-        "pt_create": (c_int, [c_int, c_uint32, c_uint32, POINTER(ctx)]),
-        "pt_resize_clear": (c_int, [ctx, c_uint32, c_uint32]),
-        "pt_set_program": (c_int, [ctx, POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, c_uint32]),
-        "pt_set_data": (c_int, [ctx, POINTER(c_float), c_uint32]),
-        "pt_set_tiles": (c_int, [ctx, c_uint32, c_uint32]),
-        "pt_set_camera": (c_int, [ctx, POINTER(Camera)]),
-        "pt_get_camera": (c_int, [ctx, POINTER(Camera), POINTER(c_int)]),
-        "pt_set_sky": (c_int, [ctx, POINTER(Sky)]),
-        "pt_get_sky": (c_int, [ctx, POINTER(Sky), POINTER(c_int)]),
-        "pt_dispatch": (c_int, [ctx, POINTER(Constants), POINTER(Settings), c_uint32]),
-        "pt_read_accum": (c_int, [ctx, POINTER(c_float), c_size_t]),
-        "pt_accum_device_ptr": (c_int, [ctx, POINTER(c_void_p), POINTER(c_size_t)]),
-        "pt_get_size": (c_int, [ctx, u32p, u32p]),
-        "pt_comm_get_unique_id": (c_int, [POINTER(c_uint8)]),
-        "pt_comm_init": (c_int, [ctx, c_uint32, c_uint32, POINTER(c_uint8)]),
-        "pt_comm_size": (c_int, [ctx, u32p]),
-        "pt_reduce_accum": (c_int, [ctx, c_int]),
-        "pt_read_reduced": (c_int, [ctx, POINTER(c_float), c_size_t]),
-        "pt_sync": (c_int, [ctx]),
-        "pt_last_dispatch_ms": (c_int, [ctx, POINTER(c_float)]),
-        "pt_dispatch_stats": (c_int, [ctx, POINTER(Constants), POINTER(Settings), c_uint32, POINTER(c_uint64)]),
-        "pt_set_option": (c_int, [ctx, c_char_p, c_int]),
-        "pt_get_option": (c_int, [ctx, c_char_p, POINTER(ctypes.c_double)]),
-        "pt_jit_log": (c_char_p, [ctx]),
-        "pt_jit_compile": (c_int, [POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, POINTER(c_float), c_uint32, c_char_p,
-                                   c_size_t, POINTER(c_size_t)]),
-        "pt_scene_kernel_source": (c_int, [POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, POINTER(c_float), c_uint32,
-                                           c_int, c_char_p, c_size_t, POINTER(c_size_t)]),
-        "pt_last_error": (c_char_p, [ctx]),
-        "pt_destroy": (None, [ctx]),
-        "pt_abi_version": (c_int, []),
-        "pt_device_math": (c_int, [c_int, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float), c_uint32]),
-        "pt_check_sqrt_exhaustive": (c_int, [c_int, POINTER(c_uint64), POINTER(c_uint32)]),
-        "pt_check_div_exhaustive": (c_int, [c_int, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_uint64),
-                                            POINTER(c_uint64)]),
-        "pt_check_div_random": (c_int, [c_int, c_uint32, c_uint32, POINTER(c_uint64), POINTER(c_uint64)]),
-        "pt_check_box_random": (c_int, [c_int, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
-        "pt_check_div_k": (c_int, [c_int, c_float, c_uint32, c_uint32, POINTER(c_uint64), POINTER(c_uint64)]),
-        "pt_traffic_probe": (c_int, [c_int, c_uint32, POINTER(c_float), POINTER(c_uint64)]),
-        "pt_display": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
-        "pt_write_accum": (c_int, [c_void_p, POINTER(c_float), c_size_t]),
-        "pt_render_guides": (c_int, [ctx, POINTER(Constants), POINTER(Settings)]),
-        "pt_read_guides": (c_int, [ctx, POINTER(c_float), POINTER(c_float), c_size_t]),
-        "pt_denoise": (c_int, [ctx, POINTER(DenoiseParams), c_int, c_void_p, c_size_t]),
-        "pt_sample_field": (c_int, [ctx, POINTER(c_float), c_uint32, POINTER(c_float), POINTER(c_int32)]),
-        "pt_mesh_extract": (c_int, [ctx, POINTER(MeshDesc), POINTER(MeshInfo)]),
-        "pt_mesh_read": (c_int, [ctx, POINTER(c_float), POINTER(c_float), POINTER(c_int32), u32p, c_size_t, c_size_t]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIGNATURES.items():
         if os.environ.get("PT_LIB") and not hasattr(L, name):
             continue  # an older A/B variant may predate a self-test entry point
         f = getattr(L, name)
@@ -233,6 +226,15 @@ def lib() -> ctypes.CDLL:
     return L
 
 
+def ptr(array, ctype):
+    """A numpy array's data as a ``ctype`` pointer (the array must outlive the call)."""
+    return array.ctypes.data_as(POINTER(ctype))
+
+
+def fptr(array):
+    return ptr(array, c_float)
+
+
 def scene_kernel_source(prog, data=None, baked: int = 0) -> str:
     """The scene-kernel source generated for ``prog`` with ``data`` (default:
     the program's own values), not compiled: ``pt_scene_kernel_source``'s
@@ -240,7 +242,7 @@ def scene_kernel_source(prog, data=None, baked: int = 0) -> str:
     import numpy as np
 
     d = np.ascontiguousarray(prog.data if data is None else data, np.float32)
-    args = (prog.ops, prog.n_ops, prog.aabbs, prog.n_aabb, d.ctypes.data_as(POINTER(c_float)), len(d), int(baked))
+    args = (prog.ops, prog.n_ops, prog.aabbs, prog.n_aabb, fptr(d), len(d), int(baked))
     n = c_size_t()
     assert lib().pt_scene_kernel_source(*args, None, 0, ctypes.byref(n)) == PT_OK
     buf = ctypes.create_string_buffer(n.value)

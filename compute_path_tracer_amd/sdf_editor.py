@@ -85,8 +85,59 @@ class Float:
         yield self
 
 
-class V3:
+class Node:
+    """A serde struct of the editor.  ``FIELDS`` states its members once, as
+    (name, kind) in the key order of its ``to_json``: kind is Float or a Node
+    class (saved through its own to_json / from_json), ``[kind]`` for a list
+    of them, ``None`` for a plain value or a cast such as ``bool``.  FIELDS
+    names every attribute, so ``from_json`` fills a bare instance.  ``COMPILE``
+    names the members that hold Floats in the order the reference's compile
+    visits them (what ``floats()`` yields) and ``REFRESH`` in the order its
+    refresh does (default: COMPILE); the three orders differ.  Float (the
+    leaf) and Shapes (a serde enum) write their own by hand."""
+
+    FIELDS: Tuple = ()
+    COMPILE: Tuple[str, ...] = ()
+    REFRESH: Optional[Tuple[str, ...]] = None
+
+    def floats(self):
+        for name in self.COMPILE:
+            yield from getattr(self, name).floats()
+
+    def rehash(self):
+        for f in self.floats():
+            f.rehash()
+
+    def refresh(self, comp_data):
+        for name in self.COMPILE if self.REFRESH is None else self.REFRESH:
+            member = getattr(self, name)
+            for m in member if isinstance(member, list) else (member,):
+                m.refresh(comp_data)
+
+    def to_json(self):
+        def save(v):
+            return [save(x) for x in v] if isinstance(v, list) else v.to_json() if hasattr(v, "to_json") else v
+
+        return {name: save(getattr(self, name)) for name, _ in self.FIELDS}
+
+    @classmethod
+    def from_json(cls, d):
+        def load(kind, v):
+            if isinstance(kind, list):
+                return [load(kind[0], x) for x in v]
+            return v if kind is None else kind.from_json(v) if hasattr(kind, "from_json") else kind(v)
+
+        node = cls.__new__(cls)
+        for name, kind in cls.FIELDS:
+            setattr(node, name, load(kind, d[name]))
+        return node
+
+
+class V3(Node):
     """primitives.rs:269-331."""
+
+    FIELDS = (("x", Float), ("y", Float), ("z", Float), ("name", None))
+    COMPILE = ("x", "y", "z")
 
     def __init__(self, x: Float, y: Float, z: Float, name: str):
         self.x, self.y, self.z, self.name = x, y, z, name
@@ -105,25 +156,14 @@ class V3:
     def set(self, v) -> None:
         self.x.set(v[0]); self.y.set(v[1]); self.z.set(v[2])
 
-    def floats(self):
-        yield self.x
-        yield self.y
-        yield self.z
 
-    def rehash(self):
-        for f in self.floats():
-            f.rehash()
-
-    def to_json(self):
-        return {"x": self.x.to_json(), "y": self.y.to_json(), "z": self.z.to_json(), "name": self.name}
-
-    @classmethod
-    def from_json(cls, d):
-        return cls(Float.from_json(d["x"]), Float.from_json(d["y"]), Float.from_json(d["z"]), d["name"])
-
-
-class Transform:
+class Transform(Node):
     """data_structures.rs:10-111."""
+
+    FIELDS = (("position", V3), ("rotation", V3), ("scale", Float), ("aabb_exaggeration", Float), ("aabb", bool))
+    COMPILE = ("scale", "position", "rotation", "aabb_exaggeration")  # Transform::compile
+    # data_structures.rs:98-103 (with shared hashes the last write wins, so the order matters)
+    REFRESH = ("position", "rotation", "scale", "aabb_exaggeration")
 
     def __init__(self):
         self.position = V3.xyz("Position", S2, 0.0)
@@ -132,45 +172,14 @@ class Transform:
         self.aabb_exaggeration = Float.new("AABB_exaggeration", S2, 1.3, (0.0, 10.0))
         self.aabb = True
 
-    def floats(self):
-        # Transform::compile order: scale, position, rotation, aabb_exaggeration
-        yield self.scale
-        yield from self.position.floats()
-        yield from self.rotation.floats()
-        yield self.aabb_exaggeration
 
-    def rehash(self):
-        for f in self.floats():
-            f.rehash()
-
-    def refresh(self, comp_data):
-        """data_structures.rs:98-103 (position, rotation, scale, exaggeration:
-        with shared hashes the last write wins, so the order matters)."""
-        for f in (*self.position.floats(), *self.rotation.floats(), self.scale, self.aabb_exaggeration):
-            f.refresh(comp_data)
-
-    def to_json(self):
-        return {"position": self.position.to_json(), "rotation": self.rotation.to_json(),
-                "scale": self.scale.to_json(), "aabb_exaggeration": self.aabb_exaggeration.to_json(),
-                "aabb": self.aabb}
-
-    @classmethod
-    def from_json(cls, d):
-        t = cls()
-        t.position = V3.from_json(d["position"])
-        t.rotation = V3.from_json(d["rotation"])
-        t.scale = Float.from_json(d["scale"])
-        t.aabb_exaggeration = Float.from_json(d["aabb_exaggeration"])
-        t.aabb = bool(d["aabb"])
-        return t
-
-
-MATERIAL_FIELDS = ("color", "brightness", "light_col", "specular_chance", "specular_color", "roughness", "ior",
-                   "refract_chance", "refract_roughness", "refract_color")
-
-
-class Material:
+class Material(Node):
     """data_structures.rs:115-221 (Mat order of test_compute.glsl:45-59)."""
+
+    FIELDS = (("color", V3), ("brightness", Float), ("light_col", V3), ("specular_chance", Float),
+              ("specular_color", V3), ("roughness", Float), ("ior", Float), ("refract_chance", Float),
+              ("refract_roughness", Float), ("refract_color", V3))
+    COMPILE = tuple(name for name, _ in FIELDS)
 
     def __init__(self):
         self.color = V3.rgb("Surface Color")
@@ -184,31 +193,17 @@ class Material:
         self.refract_roughness = Float.inv("Refract roughness", S1, 0.0)
         self.refract_color = V3.rgb("Refract color")
 
-    def floats(self):
-        for name in MATERIAL_FIELDS:
-            yield from getattr(self, name).floats()
-
     def values(self) -> List[float]:
         return [f.val for f in self.floats()]
 
-    def rehash(self):
-        for f in self.floats():
-            f.rehash()
 
-    def to_json(self):
-        return {name: getattr(self, name).to_json() for name in MATERIAL_FIELDS}
-
-    @classmethod
-    def from_json(cls, d):
-        m = cls()
-        for name in MATERIAL_FIELDS:
-            v = d[name]
-            setattr(m, name, V3.from_json(v) if "x" in v else Float.from_json(v))
-        return m
+MATERIAL_FIELDS = Material.COMPILE
 
 
-class Shapes:
-    """containers.rs:259-319 (Sphere, Cube, Plane) + Torus/Octahedron extensions."""
+class Shapes(Node):
+    """containers.rs:259-319 (Sphere, Cube, Plane) + Torus/Octahedron
+    extensions.  A serde enum, not a struct: its Floats are the ``params``
+    list and its to_json / from_json write the enum forms out by hand."""
 
     SPHERE, CUBE, PLANE, TORUS, OCTAHEDRON = "Sphere", "Cube", "Plane", "Torus", "Octahedron"
     KIND = {SPHERE: N.PT_NODE_SPHERE, CUBE: N.PT_NODE_CUBE, PLANE: N.PT_NODE_PLANE, TORUS: N.PT_NODE_TORUS,
@@ -232,16 +227,15 @@ class Shapes:
     def floats(self):
         yield from self.params
 
-    def rehash(self):
+    def refresh(self, comp_data):
         for f in self.params:
-            f.rehash()
+            f.refresh(comp_data)
 
     def to_json(self):
         if self.kind == self.PLANE:
             return "Plane"
         if self.kind == self.CUBE:
-            x, y, z = self.params
-            return {"Cube": {"x": x.to_json(), "y": y.to_json(), "z": z.to_json(), "name": "Size"}}
+            return {"Cube": V3(*self.params, "Size").to_json()}
         if self.kind == self.TORUS:
             return {"Torus": [p.to_json() for p in self.params]}
         return {self.kind: self.params[0].to_json()}
@@ -258,8 +252,12 @@ class Shapes:
         return cls(kind, [Float.from_json(v)])
 
 
-class Shape:
+class Shape(Node):
     """containers.rs:322-476."""
+
+    FIELDS = (("transform", Transform), ("material", Material), ("current_shape", Shapes), ("name", None))
+    COMPILE = ("transform", "current_shape", "material")  # Shape::compile: transform, shape settings, material
+    REFRESH = ("transform", "material", "current_shape")  # containers.rs:466-470: the shape's size last
 
     def __init__(self, kind: str = Shapes.SPHERE):
         self.transform = Transform()
@@ -267,42 +265,17 @@ class Shape:
         self.current_shape = Shapes(kind)
         self.name = "Shape"
 
-    def floats(self):
-        # Shape::compile order: transform, shape settings, material
-        yield from self.transform.floats()
-        yield from self.current_shape.floats()
-        yield from self.material.floats()
-
-    def rehash(self):
-        self.transform.rehash(); self.material.rehash(); self.current_shape.rehash()
-
-    def refresh(self, comp_data):
-        """containers.rs:466-470: transform, material, then the shape's size."""
-        self.transform.refresh(comp_data)
-        for f in (*self.material.floats(), *self.current_shape.floats()):
-            f.refresh(comp_data)
-
-    def to_json(self):
-        return {"transform": self.transform.to_json(), "material": self.material.to_json(),
-                "current_shape": self.current_shape.to_json(), "name": self.name}
-
-    @classmethod
-    def from_json(cls, d):
-        s = cls()
-        s.transform = Transform.from_json(d["transform"])
-        s.material = Material.from_json(d["material"])
-        s.current_shape = Shapes.from_json(d["current_shape"])
-        s.name = d["name"]
-        return s
-
 
 class UnionType:
     UNION = "Union"
     SUBTRACTION = "Subtraction"
 
 
-class Union:
+class Union(Node):
     """containers.rs:8-203."""
+
+    COMPILE = ("transform",)  # (the union's own Floats; its children are nodes of their own)
+    REFRESH = ("transform", "children_shapes", "children_unions")  # containers.rs:204-212
 
     def __init__(self, union_type: str = UnionType.UNION):
         self.name = "Union"
@@ -311,27 +284,9 @@ class Union:
         self.children_unions: List[Union] = []
         self.children_shapes: List[Shape] = []
 
-    def refresh(self, comp_data):
-        """containers.rs:204-212: transform, shapes, then child unions."""
-        self.transform.refresh(comp_data)
-        for s in self.children_shapes:
-            s.refresh(comp_data)
-        for u in self.children_unions:
-            u.refresh(comp_data)
 
-    def to_json(self):
-        return {"name": self.name, "transform": self.transform.to_json(), "union_type": self.union_type,
-                "children_unions": [u.to_json() for u in self.children_unions],
-                "children_shapes": [s.to_json() for s in self.children_shapes]}
-
-    @classmethod
-    def from_json(cls, d):
-        u = cls(d["union_type"])
-        u.name = d["name"]
-        u.transform = Transform.from_json(d["transform"])
-        u.children_unions = [Union.from_json(c) for c in d["children_unions"]]
-        u.children_shapes = [Shape.from_json(c) for c in d["children_shapes"]]
-        return u
+Union.FIELDS = (("name", None), ("transform", Transform), ("union_type", None), ("children_unions", [Union]),
+                ("children_shapes", [Shape]))  # (after the class: it names itself)
 
 
 class DataArray:
@@ -402,34 +357,42 @@ class Program:
     data: np.ndarray = field(default_factory=lambda: np.zeros(1, np.float32))
 
     def op_dicts(self) -> List[dict]:
-        out = []
-        for i in range(self.n_ops):
-            o = self.ops[i]
-            out.append({"opcode": o.opcode, "shape": o.shape, "combine": o.combine, "check": o.check,
-                        "scale": o.scale, "position": list(o.position), "rotation": list(o.rotation),
-                        "aabb_exaggeration": o.aabb_exaggeration, "size": list(o.size),
-                        "material": list(o.material)})
-        return out
+        return [struct_dict(self.ops[i]) for i in range(self.n_ops)]
 
     def aabb_dicts(self) -> List[dict]:
-        out = []
-        for i in range(self.n_aabb):
-            a = self.aabbs[i]
-            out.append({"back": a.back, "so_kind": a.so_kind, "union_position": list(a.union_position),
-                        "union_scale": a.union_scale, "shape_position": list(a.shape_position),
-                        "shape_scale": a.shape_scale, "size": list(a.size),
-                        "aabb_exaggeration": a.aabb_exaggeration})
-        return out
+        return [struct_dict(self.aabbs[i]) for i in range(self.n_aabb)]
 
 
-def node_keys(t: Transform, size: List[Float], material: Optional[Material]) -> List[int]:
-    """The node's Float hashes in pt_float_key order (PT_NODE_FLOATS): scale,
-    position xyz, rotation xyz, exaggeration, size[3], material[18]; 0 where
-    the node has no such Float."""
-    keys = [f.hash for f in t.floats()]
-    keys += [f.hash for f in size] + [0] * (3 - len(size))
-    keys += [f.hash for f in material.floats()] if material is not None else [0] * 18
-    return keys
+def struct_dict(s: ctypes.Structure) -> dict:
+    """A ctypes structure as a dict in ``_fields_`` order: scalars as ints, arrays as lists."""
+    return {name: list(getattr(s, name)) if issubclass(t, ctypes.Array) else getattr(s, name)
+            for name, t in s._fields_}
+
+
+def key_floats(node) -> List[Optional[Float]]:
+    """A Union's or Shape's Floats in pt_float_key order (PT_NODE_FLOATS):
+    scale, position xyz, rotation xyz, exaggeration, size[3], material[18];
+    None where the node has no such Float (a union has the first 8)."""
+    size = list(node.current_shape.floats()) if isinstance(node, Shape) else []
+    material = list(node.material.floats()) if isinstance(node, Shape) else [None] * 18
+    return [*node.transform.floats(), *size, *[None] * (3 - len(size)), *material]
+
+
+def node_keys(node) -> List[int]:
+    """The node's Float hashes in pt_float_key order; 0 where it has no such Float."""
+    return [0 if f is None else f.hash for f in key_floats(node)]
+
+
+def node_row(node, parent: int) -> dict:
+    """One row of ``flatten``: the pt_scene_node of a Union or Shape, its
+    values in key_floats order (0 where it has no such Float), and its keys."""
+    v = [0.0 if f is None else f.val for f in key_floats(node)]
+    is_union = isinstance(node, Union)
+    return {"kind": N.PT_NODE_UNION if is_union else Shapes.KIND[node.current_shape.kind], "parent": parent,
+            "union_type": N.PT_UNION_TYPE_SUBTRACTION if is_union and node.union_type == UnionType.SUBTRACTION
+            else N.PT_UNION_TYPE_UNION, "aabb": int(node.transform.aabb), "scale": v[0], "position": v[1:4],
+            "rotation": v[4:7], "aabb_exaggeration": v[7], "size": v[8:11], "material": v[11:],
+            "keys": node_keys(node)}
 
 
 def keys_to_ctypes(rows: List[dict]):
@@ -452,24 +415,12 @@ def flatten(header_unions: List[Union]) -> Tuple[List[dict], List[object]]:
 
     def visit(u: Union, parent: int):
         idx = len(rows)
-        t = u.transform
-        rows.append({"kind": N.PT_NODE_UNION, "parent": parent,
-                     "union_type": N.PT_UNION_TYPE_SUBTRACTION if u.union_type == UnionType.SUBTRACTION
-                     else N.PT_UNION_TYPE_UNION, "aabb": int(t.aabb), "scale": t.scale.val,
-                     "position": t.position.vals(), "rotation": t.rotation.vals(),
-                     "aabb_exaggeration": t.aabb_exaggeration.val, "size": [0.0, 0.0, 0.0],
-                     "material": [0.0] * 18, "keys": node_keys(t, [], None)})
+        rows.append(node_row(u, parent))
         objs.append(u)
         for c in u.children_unions:
             visit(c, idx)
         for s in u.children_shapes:
-            st = s.transform
-            sz = [p.val for p in s.current_shape.params] + [0.0] * (3 - len(s.current_shape.params))
-            rows.append({"kind": Shapes.KIND[s.current_shape.kind], "parent": idx, "union_type": 0,
-                         "aabb": int(st.aabb), "scale": st.scale.val, "position": st.position.vals(),
-                         "rotation": st.rotation.vals(), "aabb_exaggeration": st.aabb_exaggeration.val,
-                         "size": sz, "material": s.material.values(),
-                         "keys": node_keys(st, s.current_shape.params, s.material)})
+            rows.append(node_row(s, idx))
             objs.append(s)
 
     for u in header_unions:
@@ -480,16 +431,8 @@ def flatten(header_unions: List[Union]) -> Tuple[List[dict], List[object]]:
 def nodes_to_ctypes(rows: List[dict]) -> ctypes.Array:
     arr = (N.SceneNode * max(1, len(rows)))()
     for i, r in enumerate(rows):
-        n = arr[i]
-        n.kind, n.parent, n.union_type, n.aabb = r["kind"], r["parent"], r["union_type"], r["aabb"]
-        n.scale = r["scale"]
-        n.aabb_exaggeration = r["aabb_exaggeration"]
-        for k in range(3):
-            n.position[k] = r["position"][k]
-            n.rotation[k] = r["rotation"][k]
-            n.size[k] = r["size"][k]
-        for k in range(18):
-            n.material[k] = r["material"][k]
+        for name, t in N.SceneNode._fields_:
+            setattr(arr[i], name, t(*r[name]) if issubclass(t, ctypes.Array) else r[name])
     return arr
 
 
@@ -507,8 +450,8 @@ def compile_rows(rows: List[dict]) -> Program:
     aabbs = (N.Aabb * max(1, n_aabb.value))()
     data = np.zeros(n_data.value, dtype=np.float32)
     rc = L.pt_compile_scene_keyed(nodes, len(rows), keys, ops, n_ops.value, ctypes.byref(n_ops), aabbs, n_aabb.value,
-                                  ctypes.byref(n_aabb), data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                  n_data.value, ctypes.byref(n_data), ctypes.byref(n_check))
+                                  ctypes.byref(n_aabb), N.fptr(data), n_data.value, ctypes.byref(n_data),
+                                  ctypes.byref(n_check))
     N.check("pt_compile_scene_keyed", rc)
     return Program(ops, aabbs, n_ops.value, n_aabb.value, n_check.value, data)
 
@@ -533,24 +476,19 @@ class SDFEditor:
         rows, objs = flatten(self.header_unions)
         prog = compile_rows(rows)
         # register Float -> slot exactly as Float::compile would have
-        shape_ops = [o for o in prog.op_dicts() if o["opcode"] == N.PT_OP_SHAPE]
-        union_ops = [o for o in prog.op_dicts() if o["opcode"] == N.PT_OP_UNION_BEGIN]
+        ops = prog.op_dicts()
+        shape_ops = [o for o in ops if o["opcode"] == N.PT_OP_SHAPE]
+        union_ops = [o for o in ops if o["opcode"] == N.PT_OP_UNION_BEGIN]
+        next_op = {Shape: iter(shape_ops), Union: iter(union_ops)}
         data = comp_data.data_array
         data.data = [float(x) for x in prog.data]
-        ui = si = 0
         for obj in objs:
-            if isinstance(obj, Union):
-                op = union_ops[ui]; ui += 1
-            else:
-                op = shape_ops[si]; si += 1
-            slots = [op["scale"], *op["position"], *op["rotation"], op["aabb_exaggeration"]]
-            fl = list(obj.transform.floats())
-            if isinstance(obj, Shape):
-                nsz = len(obj.current_shape.params)
-                slots += op["size"][:nsz] + op["material"]
-                fl += list(obj.current_shape.floats()) + list(obj.material.floats())
-            for f, sl in zip(fl, slots):
-                data.seen[f.hash] = sl
+            op = next(next_op[type(obj)])
+            slots = [op["scale"], *op["position"], *op["rotation"], op["aabb_exaggeration"], *op["size"],
+                     *op["material"]]  # (pt_op's operands are in pt_float_key order)
+            for f, slot in zip(key_floats(obj), slots):
+                if f is not None:
+                    data.seen[f.hash] = slot
         comp_data.aabb_index = prog.n_check if prog.n_check > 1 or shape_ops else 0
         return prog
 
