@@ -80,6 +80,13 @@ class DenoiseParams(Structure):
                 ("sigma_depth", c_float), ("sigma_albedo", c_float)]
 
 
+class GuidedParams(Structure):
+    """pt_guided_params: the variance-guided filter of ``pt_denoise_guided`` (new)."""
+
+    _fields_ = [("iterations", c_uint32), ("normal_power_log2", c_uint32), ("sigma_variance", c_float),
+                ("sigma_depth", c_float), ("sigma_albedo", c_float)]
+
+
 PT_MESH_BRICK, PT_MESH_MAX_CELLS, PT_MESH_MAX_PROJECT = 8, 1024, 8
 
 
@@ -134,6 +141,7 @@ class Aabb(Structure):
 
 assert ctypes.sizeof(Constants) == 16 and ctypes.sizeof(Settings) == 20
 assert ctypes.sizeof(Camera) == 56 and ctypes.sizeof(Sky) == 52 and ctypes.sizeof(DenoiseParams) == 20
+assert ctypes.sizeof(GuidedParams) == 20
 assert ctypes.sizeof(MeshDesc) == 36 and ctypes.sizeof(MeshInfo) == 48
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
@@ -191,6 +199,10 @@ SIGNATURES = {
     "pt_render_guides": (c_int, [_ctx, POINTER(Constants), POINTER(Settings)]),
     "pt_read_guides": (c_int, [_ctx, _f32p, _f32p, c_size_t]),
     "pt_denoise": (c_int, [_ctx, POINTER(DenoiseParams), c_int, c_void_p, c_size_t]),
+    "pt_read_moments": (c_int, [_ctx, _f32p, c_size_t]),
+    "pt_write_moments": (c_int, [_ctx, _f32p, c_size_t, c_uint32]),
+    "pt_read_variance": (c_int, [_ctx, _f32p, c_size_t]),
+    "pt_denoise_guided": (c_int, [_ctx, POINTER(GuidedParams), c_int, c_void_p, c_size_t]),
     "pt_sample_field": (c_int, [_ctx, _f32p, c_uint32, _f32p, POINTER(c_int32)]),
     "pt_mesh_extract": (c_int, [_ctx, POINTER(MeshDesc), POINTER(MeshInfo)]),
     "pt_mesh_read": (c_int, [_ctx, _f32p, _f32p, POINTER(c_int32), _u32p, c_size_t, c_size_t]),

@@ -154,6 +154,7 @@ struct BinPlan {
     bool stats = false, posed = false;
     bool use_table = false;   // bins from the table of check[] sets
     bool taps_shade = false;  // normal taps in the shade pass: march-only trace + tapping shade (scene kernels)
+    float *moments = nullptr;  // the fold also keeps the moment image (pt_set_option "moments")
     const PtJitModule *jm = nullptr;
     hipFunction_t trace = nullptr, trace_first = nullptr;
     unsigned cu = 1, trace_grid = 1, trace_g_grid = 1, shade_grid = 1;
@@ -425,7 +426,9 @@ int encode_chunk(pt_ctx *c, const BinPlan &pl, const PtLaunch &L, uint32_t done,
     Fp.color = b.color.as<float4>();
     Fp.frames = int32_t(fr);
     Fp.lanes = nl;  // (the colour regions' split: bin_fold_body)
-    pt_launch_bin(PtBinStage::Fold, Fp, pl.stats, unsigned((pl.n_pix + PT_BIN_BLOCK - 1) / PT_BIN_BLOCK), c->stream);
+    const unsigned fold_grid = unsigned((pl.n_pix + PT_BIN_BLOCK - 1) / PT_BIN_BLOCK);
+    if (pl.moments) pt_launch_bin_fold_m(Fp, pl.moments, fold_grid, c->stream);
+    else pt_launch_bin(PtBinStage::Fold, Fp, pl.stats, fold_grid, c->stream);
     HIPCHK(c, hipGetLastError());
     return PT_OK;
 }
@@ -433,11 +436,12 @@ int encode_chunk(pt_ctx *c, const BinPlan &pl, const PtLaunch &L, uint32_t done,
 }  // namespace
 
 // One dispatch through the pass pipeline, chunk by chunk.
-int pt_launch_binned(pt_ctx *c, PtLaunch &L, bool stats) {
+int pt_launch_binned(pt_ctx *c, PtLaunch &L, bool stats, float *moments) {
     BinState &b = c->bin;
     BinPlan pl;
     int rc = plan_dispatch(c, L, stats, pl);
     if (rc != PT_OK) return rc;
+    pl.moments = moments;
     // the set table's overflow count covers the whole dispatch (the table
     // itself is cleared per chunk)
     if (pl.use_table && stats)

@@ -182,6 +182,18 @@ struct pt_ctx {
         int lds = 1;  // pt_set_option "denoise_lds": LDS-staged taps at steps 1 and 2 (-19 % on five iterations: EXPERIMENTS.md)
         TimedSection guide_time, denoise_time;
     } dn;
+    // second moments (pt_set_option "moments"): the image M of each frame's squared colour,
+    // mixed as the accumulation image is (16 B/px, held while the option is on); whether it and the
+    // accumulation image are one render's, and of how many frames; the variance plane's two ping-pong
+    // buffers (4 B/px each, grown on first use); the timing of the variance kernel and of the guided filter
+    struct Moments {
+        int on = 0;
+        DevBuf img;
+        bool valid = false;
+        uint32_t frames = 0;
+        DevBuf var[2];
+        TimedSection variance_time, guided_time;
+    } mom;
     // mesh export (pt_sample_field / pt_mesh_extract, pt_mesh_host.cpp): the extractor's
     // working memory -- per brick: flag, slot, list; per evaluated brick: corner lattice, masks, counts and
     // bases; per vertex: its cell; the counters -- and the last mesh, all grown on first use; the timing of the stages' kernels
@@ -247,4 +259,8 @@ inline int read_back(pt_ctx *c, void *out, size_t bytes, const void *src, size_t
 // pt_bin_host.cpp: the binned pipeline's scheduler
 size_t pt_bin_bytes_per_sample(const pt_ctx *c);
 size_t pt_bin_samples(pt_ctx *c);  // samples per chunk: the option, else the automatic size
-int pt_launch_binned(pt_ctx *c, PtLaunch &L, bool stats);
+// moments: the moment image the folds keep beside the accumulation image (nullptr: the plain fold)
+int pt_launch_binned(pt_ctx *c, PtLaunch &L, bool stats, float *moments);
+// pt_runtime.hip: the moment image sized to the accumulation image and zeroed while the option is on, and not
+// valid (the option's setter, pt_resize_clear, pt_set_tiles)
+int pt_moments_reset(pt_ctx *c);

@@ -39,6 +39,28 @@ struct PtAtrous {
     float kc[PT_DENOISE_MAX_ITERATIONS], kz[PT_DENOISE_MAX_ITERATIONS];
 };
 void pt_launch_atrous(const PtAtrous &A, bool lds, hipStream_t stream);
+// second moments (pt_set_option "moments"): the simple kernel and the binned fold that also mix
+// each frame's squared colour into the moment image (debug 0, write 1 only; launched instead of pt_render_kernel /
+// pt_bin_fold_kernel while the option is on)
+void pt_launch_render_m(const PtLaunch &L, float *moments, hipStream_t stream);
+void pt_launch_bin_fold_m(const PtPass &P, float *moments, unsigned grid, hipStream_t stream);
+// v[i] = ((vr + vg) + vb), v.k = max(M.k - A.k * A.k, 0) / nm1, over n texels (pt_read_variance)
+void pt_launch_variance(const float *accum, const float *moments, float *v, uint32_t n, float nm1, hipStream_t stream);
+// one iteration of the variance-guided filter (pt_denoise_guided): PtAtrous's taps with a per-pixel colour
+// constant from the 3x3-smoothed variance plane, which is filtered beside the colour (vin -> vout)
+struct PtGuided {
+    const float4 *in, *g0, *g1;
+    const float *vin;
+    float4 *out;
+    float *vout;
+    int32_t w, h;
+    int32_t iter;   // taps at step 1 << iter
+    int32_t npow;   // normal_power_log2
+    float ka;
+    float sv2;      // sigma_variance squared
+    float kz[PT_DENOISE_MAX_ITERATIONS];
+};
+void pt_launch_guided(const PtGuided &A, bool lds, hipStream_t stream);  // lds: staged taps at steps 1 and 2
 
 // Expand (program, data[]) into the device tables (see pt_device.h).
 int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, const float *data, uint32_t n,

@@ -41,6 +41,16 @@ int set_jit_wait(pt_ctx *c, int) {  // block until a pending tier-up build is in
     return PT_OK;
 }
 
+// "moments" (DESIGN.md 3.28): switching it on allocates and zeroes the moment image, switching it off drops
+// the moments' validity (the buffer is kept for the next time); setting the value it has changes nothing
+int set_moments(pt_ctx *c, int value) {
+    if (value < 0 || value > 1) return fail(c, PT_ERR_INVALID, "moments must be 0 or 1");
+    if ((value != 0) == (c->mom.on != 0)) return PT_OK;
+    c->mom.on = value ? 1 : 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    return pt_moments_reset(c);
+}
+
 // Waves per SIMD the scene kernel in use can hold: 8 = the 8-wave build
 // (<= 64 VGPRs), 7 = the rebuild after a spill (pt_jit_compile_source)
 double jit_waves(pt_ctx *c, PtJitStage stage, int threads) {
@@ -110,6 +120,9 @@ const Option kOptions[] = {
     OPT_INT("shade_taps", bin.shade_taps, 0, 1, "shade_taps must be 0 or 1"),
     OPT_INT("denoise_lds", dn.lds, 0, 1, "denoise_lds must be 0 or 1"),
     OPT_INT("mesh_skip", mesh.skip, 0, 1, "mesh_skip must be 0 or 1"),
+    // set through its own setter (the moment image comes and goes with it), read as it is
+    {"moments", nullptr, 0, 0, nullptr, set_moments,
+     [](pt_ctx *c, const char *, double *v) { return int((*v = double(c->mom.on), PT_OK)); }, false},
     // set only
     {"jit", FIELD(jit.enabled), 0, 1, "jit must be 0 or 1", set_jit, nullptr, false},
     {"jit_bake", FIELD(jit.bake), 0, 2, "jit_bake must be 0, 1 or 2", nullptr, nullptr, false},  // (at the next pt_set_data)
@@ -155,6 +168,12 @@ const Option kOptions[] = {
     OPT_GET("mesh_emit_ms", section_ms(c, c->mesh.stage_time[pt_ctx::Mesher::kEmit], false, v)),
     OPT_GET("mesh_ms", mesh_ms(c, v)),
     OPT_READ("guides_valid", c->dn.guides_valid ? 1.0 : 0.0),
+    // second moments: whether the moment image and the accumulation image are one render's, and of how many frames;
+    // the last variance kernel, and all iterations of the last pt_denoise_guided (without its variance and display passes)
+    OPT_READ("moments_valid", c->mom.valid ? 1.0 : 0.0),
+    OPT_READ("moment_frames", c->mom.valid ? c->mom.frames : 0u),
+    OPT_GET("variance_ms", section_ms(c, c->mom.variance_time, true, v)),
+    OPT_GET("guided_ms", section_ms(c, c->mom.guided_time, true, v)),
     OPT_GET("tap_stat_", tap_stat(c, key_, v)),
 };
 

@@ -27,6 +27,7 @@ static_assert(PT_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "RCCL unique id size");
 static_assert(sizeof(pt_camera) == 14 * 4, "pt_camera layout");
 static_assert(sizeof(pt_sky) == 13 * 4, "pt_sky layout");
 static_assert(sizeof(pt_denoise_params) == 5 * 4, "pt_denoise_params layout");
+static_assert(sizeof(pt_guided_params) == 5 * 4, "pt_guided_params layout");
 
 static int alloc_image(pt_ctx *c, uint32_t w, uint32_t h) {
     c->img.accum.release();
@@ -37,9 +38,21 @@ static int alloc_image(pt_ctx *c, uint32_t w, uint32_t h) {
     int rc = ensure(c, c->img.accum, bytes);
     if (rc != PT_OK) return rc;
     HIPCHK(c, hipMemsetAsync(c->img.accum.p, 0, bytes, c->stream));
-    return PT_OK;
+    return pt_moments_reset(c);
 }
 
+// The moment image follows the accumulation image: its size, zeroed, while
+// the option is on; either way the moments are no longer valid.
+int pt_moments_reset(pt_ctx *c) {
+    c->mom.valid = false;
+    c->mom.frames = 0;
+    if (!c->mom.on) return PT_OK;
+    const size_t bytes = std::max<size_t>(c->img.bytes(), 16);
+    const int rc = ensure(c, c->mom.img, bytes);
+    if (rc != PT_OK) return rc;
+    HIPCHK(c, hipMemsetAsync(c->mom.img.p, 0, bytes, c->stream));
+    return PT_OK;
+}
 
 extern "C" {
 
@@ -74,7 +87,7 @@ static int resize_clear(pt_ctx *c, uint32_t width, uint32_t height) {
     HIPCHK(c, hipSetDevice(c->device));
     if (width == c->img.width && height == c->img.height) {
         HIPCHK(c, hipMemsetAsync(c->img.accum.p, 0, std::max<size_t>(c->img.bytes(), 16), c->stream));
-        return PT_OK;
+        return pt_moments_reset(c);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return alloc_image(c, width, height);
@@ -222,10 +235,15 @@ static bool use_binned(const PtLaunch &L) { return L.kernel == PT_KERNEL_BINNED 
 
 // Launch one chunk: the scene-specialised wavefront kernel when loaded, else
 // the ahead-of-time kernels (pt_kernel.hip).
-static int launch(pt_ctx *c, PtLaunch &L, bool stats) {
-    if (use_binned(L)) return pt_launch_binned(c, L, stats);
+// moments: the launch also keeps the moment image (pt_dispatch: a path-traced
+// writing launch of the binned pipeline or the simple kernel, nothing else).
+static int launch(pt_ctx *c, PtLaunch &L, bool stats, float *moments = nullptr) {
+    if (use_binned(L)) return pt_launch_binned(c, L, stats, moments);
     const PtJitModule *jm = pt_jit_active(c->jit);
-    if (!pt_use_simple_kernel(L) && jm) {
+    if (moments) {
+        pt_launch_render_m(L, moments, c->stream);
+        HIPCHK(c, hipGetLastError());
+    } else if (!pt_use_simple_kernel(L) && jm) {
         void *args[] = {&L};
         HIPCHK(c, hipModuleLaunchKernel(pt_jit_select(*jm, PtJitStage::Render, stats, false, false, false),
                                         unsigned(L.n_tiles), 1, 1, 64, 1, 1, 0, c->stream, args, nullptr));
@@ -287,8 +305,23 @@ int pt_dispatch(pt_ctx *c, const pt_constants *k, const pt_settings *s, uint32_t
     PtLaunch L;
     int rc = make_launch(c, k, s, spp, L);
     if (rc != PT_OK) return rc;
+    // second moments: a path-traced dispatch keeps the moment image too.  The wave kernel does
+    // not serve it: the automatic choice is the binned pipeline whatever the size, and asking for the wave
+    // kernel is refused before anything is touched
+    const bool with_moments = c->mom.on && L.debug == 0;
+    if (with_moments) {
+        if (c->kernel == PT_KERNEL_WAVEFRONT)
+            return fail(c, PT_ERR_UNSUPPORTED, "the wave kernel keeps no second moments: kernel 0, 1 or 3 with moments on");
+        if (c->kernel == PT_KERNEL_AUTO) L.kernel = PT_KERNEL_BINNED;
+    }
+    float *moments = with_moments ? c->mom.img.as<float>() : nullptr;
     HIPCHK(c, hipSetDevice(c->device));
     pt_jit_poll(c->jit, false);  // switch to the values-baked kernel once it is built
+    // the moments stay valid only when this dispatch starts them (last_clear 0) or goes on from their frame
+    // count; any other writing dispatch leaves the two images apart
+    const uint32_t lc0 = uint32_t(k->last_clear);
+    const bool moments_go_on = with_moments && (lc0 == 0 || (c->mom.valid && c->mom.frames == lc0));
+    if (spp > 0) c->mom.valid = false;
     HIPCHK(c, c->dispatch_time.begin(c->stream));
     c->bin.tlog.used = c->bin.slog.used = c->bin.klog.used = 0;
     if (spp > 0 && L.n_tiles > 0) {
@@ -303,10 +336,14 @@ int pt_dispatch(pt_ctx *c, const pt_constants *k, const pt_settings *s, uint32_t
             Lc.frame0 = int32_t(uint32_t(L.frame0) + done);
             Lc.last_clear0 = int32_t(uint32_t(L.last_clear0) + done);
             if (L.debug != 0 && done + chunk < spp) continue;  // direct stores: only the last frame survives
-            if ((rc = launch(c, Lc, false)) != PT_OK) return rc;
+            if ((rc = launch(c, Lc, false, moments)) != PT_OK) return rc;
         }
     }
     HIPCHK(c, c->dispatch_time.end(c->stream));
+    if (spp > 0 && moments_go_on) {
+        c->mom.valid = true;
+        c->mom.frames = lc0 + spp;
+    }
     return PT_OK;
 }
 
@@ -341,9 +378,58 @@ int pt_write_accum(pt_ctx *c, const float *rgba, size_t bytes) {
     const size_t need = c->img.bytes();
     if (!rgba || bytes < need) return fail(c, PT_ERR_SIZE, "image buffer too small");
     HIPCHK(c, hipSetDevice(c->device));
+    c->mom.valid = false;  // (pt_write_moments, after this, says what the new image's moments are)
     if (need) HIPCHK(c, hipMemcpyAsync(c->img.accum.p, rgba, need, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
+}
+
+// ---- second moments and variance -------------------------------
+int pt_read_moments(pt_ctx *c, float *rgba, size_t bytes) {
+    if (!c) return PT_ERR_INVALID;
+    if (!c->mom.valid) return fail(c, PT_ERR_STATE, "no valid moments: set option moments and dispatch from last_clear 0");
+    return read_back(c, rgba, bytes, c->mom.img.p, c->img.bytes(), "readback buffer too small");
+}
+
+int pt_write_moments(pt_ctx *c, const float *rgba, size_t bytes, uint32_t frames) {
+    if (!c) return PT_ERR_INVALID;
+    if (!c->mom.on) return fail(c, PT_ERR_STATE, "pt_write_moments needs option moments on");
+    if (frames == 0) return fail(c, PT_ERR_INVALID, "moments of 0 frames");
+    const size_t need = c->img.bytes();
+    if (!rgba || bytes < need) return fail(c, PT_ERR_SIZE, "image buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (need) HIPCHK(c, hipMemcpyAsync(c->mom.img.p, rgba, need, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mom.valid = true;
+    c->mom.frames = frames;
+    return PT_OK;
+}
+
+// the variance plane of the two images into mom.var[0] (asynchronous, timed)
+static int launch_variance(pt_ctx *c) {
+    const size_t texels = size_t(c->img.width) * c->img.height;
+    int rc;
+    for (DevBuf &v : c->mom.var)
+        if ((rc = ensure(c, v, std::max<size_t>(texels * sizeof(float), 16))) != PT_OK) return rc;
+    HIPCHK(c, c->mom.variance_time.begin(c->stream));
+    pt_launch_variance(c->img.accum.as<float>(), c->mom.img.as<float>(), c->mom.var[0].as<float>(), uint32_t(texels),
+                       float(c->mom.frames - 1u), c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, c->mom.variance_time.end(c->stream));
+    return PT_OK;
+}
+
+static const char *const kNoVariance = "no variance: valid moments of at least 2 frames are needed";
+
+int pt_read_variance(pt_ctx *c, float *v, size_t bytes) {
+    if (!c) return PT_ERR_INVALID;
+    if (!c->mom.valid || c->mom.frames < 2) return fail(c, PT_ERR_STATE, kNoVariance);
+    const size_t need = c->img.bytes(sizeof(float));
+    if (!v || bytes < need) return fail(c, PT_ERR_SIZE, "variance buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = launch_variance(c);
+    if (rc != PT_OK) return rc;
+    return read_back(c, v, bytes, c->mom.var[0].p, need, nullptr);
 }
 
 int pt_display(pt_ctx *c, int format, void *out, size_t bytes) {
@@ -449,6 +535,75 @@ int pt_denoise(pt_ctx *c, const pt_denoise_params *p, int format, void *out, siz
         src = c->dn.filter[i & 1].as<float>();
     }
     HIPCHK(c, c->dn.denoise_time.end(c->stream));
+    const void *result = src;
+    if (format != PT_DENOISE_LINEAR) {
+        pt_launch_display(src, c->img.width, c->img.height, format, c->img.display.p, c->stream);
+        HIPCHK(c, hipGetLastError());
+        result = c->img.display.p;
+    }
+    return read_back(c, out, bytes, result, need, nullptr);
+}
+
+// The variance-guided form of pt_denoise: its formats, sizes and refusals, the colour
+// constant per pixel from the variance plane, which the iterations filter beside the colour.
+int pt_denoise_guided(pt_ctx *c, const pt_guided_params *p, int format, void *out, size_t bytes) {
+    if (!c) return PT_ERR_INVALID;
+    if (!p) return fail(c, PT_ERR_INVALID, "null denoise parameters");
+    if (format != PT_DISPLAY_RGBA32F && format != PT_DISPLAY_SRGB8 && format != PT_DENOISE_LINEAR)
+        return fail(c, PT_ERR_INVALID, "bad denoise format");
+    if (p->iterations < 1 || p->iterations > PT_DENOISE_MAX_ITERATIONS)
+        return fail(c, PT_ERR_INVALID, "denoise iterations must be in [1, 8]");
+    if (p->normal_power_log2 > 8) return fail(c, PT_ERR_INVALID, "denoise normal_power_log2 must be in [0, 8]");
+    for (float v : {p->sigma_depth, p->sigma_albedo})
+        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "denoise sigma must be finite and >= 0");
+    if (!std::isfinite(p->sigma_variance) || !(p->sigma_variance > 0.0f))
+        return fail(c, PT_ERR_INVALID, "denoise sigma_variance must be finite and > 0");
+    PtGuided A;
+    std::memset(&A, 0, sizeof A);
+    auto inv_sq = [](float sigma, float scale) {  // (as pt_denoise)
+        if (sigma == 0.0f) return 0.0f;
+        const float v = sigma * scale;
+        const float sq = v * v;
+        return 1.0f / sq;
+    };
+    A.ka = inv_sq(p->sigma_albedo, 1.0f);
+    bool finite = std::isfinite(A.ka);
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        A.kz[i] = inv_sq(p->sigma_depth, std::ldexp(1.0f, int(i)));
+        finite = finite && std::isfinite(A.kz[i]);
+    }
+    if (!finite) return fail(c, PT_ERR_INVALID, "denoise sigma too small: 1 / sigma^2 is not finite");
+    A.sv2 = p->sigma_variance * p->sigma_variance;
+    if (!c->dn.guides_valid) return fail(c, PT_ERR_STATE, "guides stale: call pt_render_guides");
+    if (!c->mom.valid || c->mom.frames < 2) return fail(c, PT_ERR_STATE, kNoVariance);
+    const size_t texels = size_t(c->img.width) * c->img.height;
+    const size_t need = texels * (format == PT_DISPLAY_SRGB8 ? 4 : 16);
+    if (!out || bytes < need) return fail(c, PT_ERR_SIZE, "denoise output buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    for (DevBuf &f : c->dn.filter)
+        if ((rc = ensure(c, f, std::max<size_t>(texels * 16, 16))) != PT_OK) return rc;
+    if (format != PT_DENOISE_LINEAR && (rc = ensure(c, c->img.display, std::max<size_t>(need, 16))) != PT_OK) return rc;
+    if ((rc = launch_variance(c)) != PT_OK) return rc;  // -> var[0]
+    A.g0 = c->dn.guides[0].as<const float4>();
+    A.g1 = c->dn.guides[1].as<const float4>();
+    A.w = int32_t(c->img.width);
+    A.h = int32_t(c->img.height);
+    A.npow = int32_t(p->normal_power_log2);
+    // accumulation image -> filter[0] -> filter[1] ..., variance var[0] -> var[1] -> var[0] ...: both images only read
+    const float *src = c->img.accum.as<float>();
+    HIPCHK(c, c->mom.guided_time.begin(c->stream));
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        A.in = reinterpret_cast<const float4 *>(src);
+        A.out = c->dn.filter[i & 1].as<float4>();
+        A.vin = c->mom.var[i & 1].as<const float>();
+        A.vout = c->mom.var[(i + 1) & 1].as<float>();
+        A.iter = int32_t(i);
+        pt_launch_guided(A, c->dn.lds != 0, c->stream);
+        HIPCHK(c, hipGetLastError());
+        src = c->dn.filter[i & 1].as<float>();
+    }
+    HIPCHK(c, c->mom.guided_time.end(c->stream));
     const void *result = src;
     if (format != PT_DENOISE_LINEAR) {
         pt_launch_display(src, c->img.width, c->img.height, format, c->img.display.p, c->stream);

@@ -170,6 +170,7 @@ class PathTracer:
 
     def set_tiles(self, rank: int, nranks: int) -> None:
         self._chk("pt_set_tiles", self._L.pt_set_tiles(self._ctx, rank, nranks))
+        self._tiles = (int(rank), int(nranks))
 
     # -- camera (new: the reference's view is fixed) ------------------------
     def _set_camera(self, cam: Optional[N.Camera]) -> None:
@@ -300,6 +301,93 @@ class PathTracer:
         out, po, nbytes = self._image(np.uint8 if output == "srgb8" else np.float32)
         self._chk("pt_denoise", self._L.pt_denoise(self._ctx, ctypes.byref(p), self.DENOISE_OUTPUTS[output], po, nbytes))
         return out
+
+    # -- second moments, variance and the variance-guided filter (new) --------
+    def read_moments(self) -> np.ndarray:
+        """pt_read_moments: the image of the frames' squared colours, mixed as
+        the accumulation image is (``set_option("moments", 1)`` before the
+        render); float32 [height][width][4], rows as read_image."""
+        out, p, nbytes = self._image()
+        self._chk("pt_read_moments", self._L.pt_read_moments(self._ctx, p, nbytes))
+        return out
+
+    def write_moments(self, m: np.ndarray, frames: int) -> None:
+        """pt_write_moments: replace the moment image and say it holds
+        ``frames`` frames of the accumulation image as it is now (after
+        write_image: resume a saved render, or hand over the host sum of a
+        multi-rank render)."""
+        _, p, nbytes = self._image(src=m)
+        self._chk("pt_write_moments", self._L.pt_write_moments(self._ctx, p, nbytes, int(frames)))
+
+    def variance(self) -> np.ndarray:
+        """pt_read_variance: the variance of the mean per pixel, summed over
+        r, g, b; float32 [height][width].  Needs valid moments of >= 2 frames."""
+        w, h = self.size
+        v = np.empty((h, w), np.float32)
+        self._chk("pt_read_variance", self._L.pt_read_variance(self._ctx, N.fptr(v), v.nbytes))
+        return v
+
+    def owned(self) -> np.ndarray:
+        """bool [height][width]: the texels of the 8x8 tiles this context renders (set_tiles)."""
+        w, h = self.size
+        rank, nranks = getattr(self, "_tiles", (0, 1))
+        ty, tx = np.arange(h)[:, None] // 8, np.arange(w)[None, :] // 8
+        return (ty * ((w + 7) // 8) + tx) % nranks == rank
+
+    def noise(self, percentile: float = 95.0) -> float:
+        """How noisy the image still is (host numpy): the ``percentile``, over
+        the owned and finite texels, of sqrt(variance) / (luminance + 0.01),
+        the luminance the plain mean of r, g, b."""
+        v, img = self.variance(), self.read_image()
+        with np.errstate(all="ignore"):
+            rel = np.sqrt(v) / (img[..., :3].mean(-1) + np.float32(0.01))
+        rel = rel[self.owned() & np.isfinite(rel)]
+        return float(np.percentile(rel, percentile)) if rel.size else 0.0
+
+    def denoise_guided(self, iterations: int = 5, sigma_variance: float = 2.0, sigma_depth: float = 0.05,
+                       sigma_albedo: float = 0.1, normal_power_log2: int = 5, output: str = "linear") -> np.ndarray:
+        """pt_denoise_guided: ``denoise`` with the colour term steered by the
+        per-pixel variance -- a tap's colour difference counts against
+        ``sigma_variance`` times the local standard deviation of the mean, so
+        a converged pixel keeps its detail and a noisy one is smoothed.  Needs
+        ``render_guides`` and valid moments of >= 2 frames; ``output`` as
+        ``denoise``.  Both images are left as they are."""
+        if output not in self.DENOISE_OUTPUTS:
+            raise ValueError(f"output must be one of {sorted(self.DENOISE_OUTPUTS)}, got {output!r}")
+        p = N.GuidedParams(iterations=int(iterations), normal_power_log2=int(normal_power_log2),
+                           sigma_variance=float(sigma_variance), sigma_depth=float(sigma_depth),
+                           sigma_albedo=float(sigma_albedo))
+        out, po, nbytes = self._image(np.uint8 if output == "srgb8" else np.float32)
+        self._chk("pt_denoise_guided", self._L.pt_denoise_guided(self._ctx, ctypes.byref(p), self.DENOISE_OUTPUTS[output],
+                                                                  po, nbytes))
+        return out
+
+    def render_until(self, noise: float, max_spp: int, batch: int = 16) -> int:
+        """Render "until the noise is below ``noise``": clear the image, switch
+        ``moments`` on, and dispatch ``batch`` frames at a time (a plain running
+        mean: the first frame's last_clear is 0) until ``noise()`` drops below
+        the bar or ``max_spp`` frames are in.  Returns the frames rendered;
+        ``render`` goes on from them."""
+        if max_spp < 2 or batch < 1:
+            raise ValueError("render_until needs max_spp >= 2 and batch >= 1")
+        self.set_option("moments", 1)
+        self.clear()
+        self.changed = False
+        done = 0
+        while done < max_spp:
+            n = min(batch, max_spp - done)
+            if done + n < 2:  # (a variance needs two frames)
+                n = 2 - done
+            c = self._constants(1 + done)
+            c.last_clear = done
+            self.constants.aspect = c.aspect
+            self.dispatch(c, n)
+            done += n
+            if self.noise() < noise:
+                break
+        self.constants.frame += done
+        self.constants.last_clear = done - 1  # render()'s next frame mixes with last_clear = done
+        return done
 
     # -- mesh export (new: field sampling and a surface-nets extractor) -------
     def sample_field(self, points):

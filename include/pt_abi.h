@@ -321,6 +321,47 @@ typedef struct {                 /* 20 bytes */
 #define PT_DENOISE_LINEAR 2
 #define PT_DENOISE_MAX_ITERATIONS 8
 int pt_denoise(pt_ctx *ctx, const pt_denoise_params *p, int format, void *out, size_t bytes);
+/* Second moments, variance and the variance-guided filter (new; DESIGN.md 3.28
+ * has the f32 steps).  With option "moments" on, every writing path-traced
+ * dispatch (debug == 0) mixes each frame's squared colour into a second
+ * RGBA32F image M of the accumulation image's size and order, with the weights
+ * the accumulation image A is mixed with (alpha 1, texels the context does not
+ * own stay 0).  The binned pipeline and the simple kernel keep it; the wave
+ * kernel does not: "kernel" 0 then resolves to the binned pipeline whatever
+ * the size, and "kernel" 2 makes pt_dispatch return PT_ERR_UNSUPPORTED with
+ * both images untouched.  M and A are "valid" together, for n frames: a
+ * dispatch with moments on and debug == 0 sets n = last_clear + spp when
+ * last_clear == 0, or when they were valid with n == last_clear; any other
+ * writing dispatch, pt_write_accum, pt_resize_clear, pt_set_tiles and
+ * switching the option off end it (the last two clears zero M as well);
+ * pt_dispatch_stats touches nothing.
+ * pt_read_moments: blocking copy of M (w*h*4 floats); PT_ERR_STATE unless valid. */
+int pt_read_moments(pt_ctx *ctx, float *rgba, size_t bytes);
+/* Replace M, say it holds `frames` frames of the accumulation image as it is
+ * now, and set valid (after pt_write_accum: resume a saved render, or hand
+ * over the host sum of a multi-rank render's images and moments).
+ * PT_ERR_STATE with the option off, PT_ERR_INVALID for frames == 0. */
+int pt_write_moments(pt_ctx *ctx, const float *rgba, size_t bytes, uint32_t frames);
+/* Variance of the mean per pixel, w*h floats in the image's order:
+ *   v.k = max(M.k - A.k * A.k, 0) / float(n - 1), V = (v.r + v.g) + v.b
+ * (a NaN difference counts as 0).  Blocking.  PT_ERR_STATE unless valid with
+ * n >= 2. */
+int pt_read_variance(pt_ctx *ctx, float *v, size_t bytes);
+/* pt_denoise with the colour term steered by the variance: pixel p's taps are
+ * divided by (1 + |dcolour|^2 kc_p), kc_p = 1 / (sigma_variance^2 g_p + 1e-10),
+ * g_p the 3x3-smoothed variance at p; the variance is filtered beside the
+ * colour with the squared weights, so later iterations see what is left. */
+typedef struct pt_guided_params { /* 20 bytes */
+    uint32_t iterations;         /* 1..8 */
+    uint32_t normal_power_log2;  /* 0..8 */
+    float sigma_variance;        /* finite, > 0: larger smooths more */
+    float sigma_depth;           /* doubled every iteration; 0 = term off */
+    float sigma_albedo;          /* 0 = term off */
+} pt_guided_params;
+/* Formats, output sizes, buffer rules and refusals as pt_denoise; also
+ * PT_ERR_STATE without valid moments of n >= 2 frames and PT_ERR_INVALID for
+ * a sigma_variance that is not finite or <= 0.  Reads A and M, writes neither. */
+int pt_denoise_guided(pt_ctx *ctx, const pt_guided_params *p, int format, void *out, size_t bytes);
 /* Mesh export (new; DESIGN.md 3.27 has the f32 steps and the orders).
  * Field sampling: map() at n caller points (xyz, 3 floats each) with every
  * check[] entry true (no bounds() cull).  d[i] = distance, shape[i] = ordinal
@@ -396,7 +437,9 @@ int pt_mesh_read(pt_ctx *ctx, float *positions, float *normals, int32_t *shapes,
  * stages a block's tile and halo in LDS for the iterations of step 1 and 2;
  * 0 loads every tap directly) and "mesh_skip" (pt_mesh_extract: 1, the
  * default, skips a brick whose centre value proves it holds no surface; 0
- * evaluates every brick).  Results are bit-identical for every value. */
+ * evaluates every brick).  Results are bit-identical for every value.
+ * "moments" (0, the default: a dispatch launches what it always did; 1: the
+ * second-moment image above is kept -- the image itself does not change). */
 int pt_set_option(pt_ctx *ctx, const char *key, int value);
 /* Read back: "jit_active" (1 when the scene-specialised kernel is loaded),
  * "jit_seconds" (last hipRTC compile time), "jit_tier_active" /
@@ -413,7 +456,10 @@ int pt_set_option(pt_ctx *ctx, const char *key, int value);
  * last pt_denoise, without its display pass), "mesh_skip", "sample_ms" (the
  * last pt_sample_field's kernel), "mesh_ms" (the last pt_mesh_extract's
  * kernels, the sum of "mesh_skip_ms", "mesh_classify_ms", "mesh_scan_ms" and
- * "mesh_emit_ms"), "guides_valid", "gen_trace" / "gen_norec"
+ * "mesh_emit_ms"), "guides_valid", "moments", "moments_valid", "moment_frames"
+ * (n; 0 while not valid), "variance_ms" (the last variance kernel, of
+ * pt_read_variance or pt_denoise_guided), "guided_ms" (all iterations of the
+ * last pt_denoise_guided, as "denoise_ms"), "gen_trace" / "gen_norec"
  * (the last timed binned dispatch's first pass made its own camera rays /
  * and stored no ray records for shade pass 0). */
 int pt_get_option(pt_ctx *ctx, const char *key, double *value);
