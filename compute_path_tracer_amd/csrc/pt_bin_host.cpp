@@ -16,6 +16,14 @@ size_t pt_bin_bytes_per_sample(const pt_ctx *c) {
     return kBinBytesPerSample + (c->prog.n_check > 64 ? kBinBytesWide : 0);
 }
 
+static bool bin_has_wide(const BinState &b) { return b.n_lanes > 0 && b.lane[0].buf[BinState::kMaskHi].p != nullptr; }
+
+// What the chunk buffers hold now: the wide buffers count from the first scene
+// with > 64 entries on, whatever the current scene is (ensure_bin keeps them).
+size_t pt_bin_bytes_held(const pt_ctx *c) {
+    return c->bin.cap * size_t(c->bin.n_lanes) * (kBinBytesPerSample + (bin_has_wide(c->bin) ? kBinBytesWide : 0));
+}
+
 hipError_t EventLog::record(hipStream_t stream) {
     if (used == ev.size()) {
         hipEvent_t e;
@@ -78,7 +86,7 @@ size_t bin_samples_free(pt_ctx *c) {
     const size_t per = pt_bin_bytes_per_sample(c);
     size_t free_b = 0, total_b = 0;
     if (!device_mem(c, free_b, total_b)) return size_t(1) << 27;
-    const size_t held = c->bin.cap * size_t(c->bin.n_lanes) * per;
+    const size_t held = pt_bin_bytes_held(c);
     const size_t cap = std::max<size_t>(size_t(1) << 20, (free_b + held) / 2 / per);
     return std::min<size_t>(size_t(1) << 29, cap);
 }
@@ -90,6 +98,9 @@ void free_bin(BinState &b) {
     b.btab.release();
     b.n_lanes = 0;
     b.cap = b.ctrl_words = 0;
+    // nothing has written the next table yet: bin_sets / bin_overflow read -1
+    // until a dispatch of the matching kind has run on it (pt_options.cpp read_btab)
+    b.btab_used = b.btab_counted = false;
 }
 
 // ensure_bin's result when the buffers' allocation itself failed (out of
@@ -102,9 +113,10 @@ constexpr int kBinNoMemory = -1000;
 int ensure_bin(pt_ctx *c, size_t samples, size_t passes, int lanes) {
     BinState &b = c->bin;
     const size_t words = size_t(PT_CTRL_STRIDE) * (passes + 1);
-    const bool wide = c->prog.n_check > 64;
-    // (mask_hi, check[] bits 64..127, exists only for scenes with > 64 entries)
-    const bool hi_ok = !wide || (b.n_lanes > 0 && b.lane[0].buf[BinState::kMaskHi].p != nullptr);
+    // (mask_hi, check[] bits 64..127, exists from the first scene with > 64 entries on: like cap
+    // and lanes it only grows, so a reallocation never holds less than the one before)
+    const bool wide = c->prog.n_check > 64 || bin_has_wide(b);
+    const bool hi_ok = !wide || bin_has_wide(b);
     if (samples <= b.cap && words <= b.ctrl_words && lanes <= b.n_lanes && hi_ok) return PT_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));  // lane 1 joins lane 0's stream before every dispatch ends
     samples = std::max(samples, b.cap);

@@ -257,7 +257,8 @@ inline int read_back(pt_ctx *c, void *out, size_t bytes, const void *src, size_t
 }
 
 // pt_bin_host.cpp: the binned pipeline's scheduler
-size_t pt_bin_bytes_per_sample(const pt_ctx *c);
+size_t pt_bin_bytes_per_sample(const pt_ctx *c);  // of the current scene (chunk sizing)
+size_t pt_bin_bytes_held(const pt_ctx *c);         // the chunk buffers as allocated ("bin_bytes")
 size_t pt_bin_samples(pt_ctx *c);  // samples per chunk: the option, else the automatic size
 // moments: the moment image the folds keep beside the accumulation image (nullptr: the plain fold)
 int pt_launch_binned(pt_ctx *c, PtLaunch &L, bool stats, float *moments);

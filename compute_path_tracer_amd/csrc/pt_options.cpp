@@ -146,7 +146,7 @@ const Option kOptions[] = {
     OPT_READ("jit_cache", c->jit.tier.module ? c->jit.tier_from : (c->jit.mod.module ? c->jit.from : -1)),
     OPT_READ("bin_chunks", c->bin.last_chunks),  // of the last timed binned dispatch
     OPT_READ("bin_fallback", c->bin.fallback ? 1.0 : 0.0),
-    OPT_READ("bin_bytes", double(c->bin.cap) * double(c->bin.n_lanes) * double(pt_bin_bytes_per_sample(c))),
+    OPT_READ("bin_bytes", pt_bin_bytes_held(c)),  // (as allocated: the wide buffers stay once a scene needed them)
     OPT_GET("bin_sets", read_btab(c, true, v)),
     OPT_GET("bin_overflow", read_btab(c, false, v)),
     OPT_READ("gen_trace", c->bin.gen_trace_used),
