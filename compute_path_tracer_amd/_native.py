@@ -42,6 +42,9 @@ STAT_NAMES = (
 
 PT_ST_COUNT = len(STAT_NAMES)  # device counters (pt_device.h PT_ST_COUNT)
 
+PT_PROBE_INTERP, PT_PROBE_TABLE, PT_PROBE_BAKED = 0, 1, 2  # which map() / bounds() a probe runs
+PT_PROBE_MAP, PT_PROBE_MAP_B0, PT_PROBE_MAP_B1 = 0, 1, 2  # pt_probe_map's variant: JitMap, JitMapB0, JitMapB1
+
 PT_MATH = {"max": 0, "min": 1, "sqrt": 2, "sqrtf": 3, "sin": 4, "cos": 5, "div": 6, "fma": 7}
 
 
@@ -149,6 +152,7 @@ assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.s
 # Every entry point include/pt_abi.h declares: name -> (restype, argtypes).
 _ctx = c_void_p
 _u32p, _f32p = POINTER(c_uint32), POINTER(c_float)
+_u64p = POINTER(c_uint64)
 SIGNATURES = {
     "pt_compile_scene": (c_int, [POINTER(SceneNode), c_uint32, POINTER(Op), c_uint32, _u32p, POINTER(Aabb), c_uint32,
                                  _u32p, _f32p, c_uint32, _u32p, _u32p]),
@@ -206,6 +210,14 @@ SIGNATURES = {
     "pt_sample_field": (c_int, [_ctx, _f32p, c_uint32, _f32p, POINTER(c_int32)]),
     "pt_mesh_extract": (c_int, [_ctx, POINTER(MeshDesc), POINTER(MeshInfo)]),
     "pt_mesh_read": (c_int, [_ctx, _f32p, _f32p, POINTER(c_int32), _u32p, c_size_t, c_size_t]),
+    "pt_probe_map": (c_int, [_ctx, c_int, c_int, c_uint32, _f32p, _u64p, _f32p, _u64p, c_int, _f32p, POINTER(c_int32),
+                             _u64p, _u64p]),
+    "pt_probe_taps": (c_int, [_ctx, c_int, c_uint32, _f32p, _u64p, _f32p, _f32p, POINTER(c_int32), _u64p, _u64p]),
+    "pt_probe_bounds": (c_int, [_ctx, c_int, c_uint32, _f32p, _f32p, c_int, _u32p, _u64p, _u64p]),
+    "pt_probe_kernel_source": (c_int, [POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, _f32p, c_uint32,
+                                       c_int, c_char_p, c_size_t, POINTER(c_size_t)]),
+    "pt_probe_jit_compile": (c_int, [POINTER(Op), c_uint32, POINTER(Aabb), c_uint32, _f32p, c_uint32, c_int, c_char_p,
+                                     c_size_t, POINTER(c_size_t)]),
 }
 SYMBOLS = tuple(SIGNATURES)
 
@@ -247,7 +259,7 @@ def fptr(array):
     return ptr(array, c_float)
 
 
-def scene_kernel_source(prog, data=None, baked: int = 0) -> str:
+def scene_kernel_source(prog, data=None, baked: int = 0, entry: str = "pt_scene_kernel_source") -> str:
     """The scene-kernel source generated for ``prog`` with ``data`` (default:
     the program's own values), not compiled: ``pt_scene_kernel_source``'s
     two-call pattern."""
@@ -256,10 +268,17 @@ def scene_kernel_source(prog, data=None, baked: int = 0) -> str:
     d = np.ascontiguousarray(prog.data if data is None else data, np.float32)
     args = (prog.ops, prog.n_ops, prog.aabbs, prog.n_aabb, fptr(d), len(d), int(baked))
     n = c_size_t()
-    assert lib().pt_scene_kernel_source(*args, None, 0, ctypes.byref(n)) == PT_OK
+    fn = getattr(lib(), entry)
+    assert fn(*args, None, 0, ctypes.byref(n)) == PT_OK
     buf = ctypes.create_string_buffer(n.value)
-    assert lib().pt_scene_kernel_source(*args, buf, n.value, ctypes.byref(n)) == PT_OK
+    assert fn(*args, buf, n.value, ctypes.byref(n)) == PT_OK
     return buf.value.decode()
+
+
+def probe_kernel_source(prog, data=None, baked: int = 0) -> str:
+    """The probe module's source (``pt_probe_kernel_source``): the scene-kernel
+    source up to its kernel list, then the probe kernels."""
+    return scene_kernel_source(prog, data, baked, entry="pt_probe_kernel_source")
 
 
 def check(fn: str, rc: int, ctx=None) -> None:

@@ -8,6 +8,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -161,6 +162,8 @@ struct pt_ctx {
         float bound_k = 0.0f;       // pt_bound_k of the uploaded scene (NaN: no map() bound)
         DevBuf stats;               // 2 x PT_ST_COUNT (second half: the shade pass's normal taps)
         unsigned long long tap_stats[PT_ST_COUNT] = {};  // last pt_dispatch_stats: the shade-pass taps' share
+        std::vector<PtNode> host_nodes;  // the uploaded tables, kept for the probe modules' source (pt_probe_source)
+        std::vector<PtAabb> host_boxes;
     } prog;
     struct View {
         // camera (pt_set_camera); cam_mode PT_CAM_DEFAULT: the reference's fixed view
@@ -214,6 +217,16 @@ struct pt_ctx {
             return n;
         }
     } mesh;
+    // the probes (pt_probe_map / pt_probe_taps / pt_probe_bounds, pt_map_probe.hip): the probe
+    // modules loaded so far by their generated source, how many were compiled and in how many seconds, and the
+    // staging of a call's inputs and outputs, grown on first use
+    struct Probe {
+        enum Buf { kXyz, kRd, kCheck, kBnd, kLiveIn, kD, kShape, kLiveOut, kMask, kSkip, kBufs };
+        std::map<std::string, PtProbeModule> mods;
+        int compiles = 0;
+        double seconds = 0.0;
+        DevBuf buf[kBufs];
+    } probe;
     struct Comm {
         ncclComm_t comm = nullptr;
         uint32_t nranks = 0;
@@ -265,3 +278,5 @@ int pt_launch_binned(pt_ctx *c, PtLaunch &L, bool stats, float *moments);
 // pt_runtime.hip: the moment image sized to the accumulation image and zeroed while the option is on, and not
 // valid (the option's setter, pt_resize_clear, pt_set_tiles)
 int pt_moments_reset(pt_ctx *c);
+// pt_map_probe.hip: unload the context's probe modules (pt_destroy, on the context's device)
+void pt_probe_unload(pt_ctx *c);

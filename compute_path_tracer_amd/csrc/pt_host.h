@@ -194,6 +194,33 @@ bool pt_jit_compile_source(const std::string &src, std::vector<char> &code, std:
 bool pt_jit_load(const std::vector<char> &code, PtJitModule &m, std::string &err);
 void pt_jit_unload(PtJitModule &m);
 
+// The probe module (pt_probe_map / pt_probe_taps / pt_probe_bounds, pt_map_probe.hip): the
+// scene's generated map() variants and bounds() under the probe kernels of pt_map_probe.h.  Each kernel has two
+// builds, `name` and the instrumented `name`_stats: `extern "C" __global__ __launch_bounds__(64) void name(PtProbe P) { pt::body, ST>(P); }`
+enum PtProbeFn { kProbeMap, kProbeMapB0, kProbeMapB1, kProbeTaps, kProbeBounds, kProbeFnCount };
+struct PtProbeKernel {
+    PtProbeFn fn;
+    const char *name, *body;
+};
+inline constexpr PtProbeKernel kProbeKernels[] = {
+    {kProbeMap, "pt_probe_map_jit", "probe_map_body<pt::JitMap"},
+    {kProbeMapB0, "pt_probe_map_b0_jit", "probe_map_body<pt::JitMapB0"},
+    {kProbeMapB1, "pt_probe_map_b1_jit", "probe_map_body<pt::JitMapB1"},
+    {kProbeTaps, "pt_probe_taps_jit", "probe_taps_body<pt::JitTaps"},
+    {kProbeBounds, "pt_probe_bounds_jit", "probe_bounds_body<pt::JitTaps"},
+};
+static_assert(sizeof kProbeKernels / sizeof kProbeKernels[0] == kProbeFnCount, "one kernel per PtProbeFn");
+struct PtProbeModule {  // one kernel of one source
+    hipModule_t module = nullptr;
+    hipFunction_t fn = nullptr;
+};
+// pt_jit_source's text up to and including the wave macros, then probe kernel `fn` (instrumented with `stats`),
+// or every probe kernel in both builds (fn < 0)
+std::string pt_probe_source(const std::vector<PtNode> &nodes, const std::vector<PtAabb> &boxes, bool fast_bounds,
+                            bool bake, int fn = -1, bool stats = false);
+// One hipRTC compile with the scene kernels' options; no rebuild rule, no on-disk cache.
+bool pt_probe_compile(const std::string &src, std::vector<char> &code, std::string &log);
+
 // A context's scene kernels and their lifecycle (pt_jit_state.cpp).  A code object
 // and where it came from: compiled by this process's hipRTC, or read from the
 // shipped on-disk cache (lib/jitcache)

@@ -756,10 +756,11 @@ void emit_kernels(std::ostringstream &o) {
 
 }  // namespace
 
-std::string pt_jit_source(const std::vector<PtNode> &nodes, const std::vector<PtAabb> &boxes, bool fast_bounds,
-                          bool bake) {
+// the scene's source up to and including the wave macros: what the scene kernels
+// (pt_jit_source) and the probe kernels (pt_probe_source) are both built on
+static void emit_scene(std::ostringstream &o, const std::vector<PtNode> &nodes, const std::vector<PtAabb> &boxes,
+                       bool fast_bounds, bool bake) {
     const std::vector<NodeInfo> info = analyse(nodes);
-    std::ostringstream o;
     o << "// generated by pt_jit.cpp from the scene op list\n";
     emit_experiment_defs(o);
     o << "#include \"pt_wave.h\"\n"
@@ -771,7 +772,30 @@ std::string pt_jit_source(const std::vector<PtNode> &nodes, const std::vector<Pt
     emit_traits(o, nodes, boxes);
     o << "}  // namespace pt\n";
     emit_waves_macros(o);
+}
+
+std::string pt_jit_source(const std::vector<PtNode> &nodes, const std::vector<PtAabb> &boxes, bool fast_bounds,
+                          bool bake) {
+    std::ostringstream o;
+    emit_scene(o, nodes, boxes, fast_bounds, bake);
     emit_kernels(o);
+    return o.str();
+}
+
+// A probe module's source: the scene's own map() variants and
+// bounds(), text for text, with probe kernels of pt_map_probe.h in place of
+// the scene kernels -- the one kernel (fn, stats) a probe call needs, so a call
+// compiles no more than it runs, or all of them (fn < 0).
+std::string pt_probe_source(const std::vector<PtNode> &nodes, const std::vector<PtAabb> &boxes, bool fast_bounds,
+                            bool bake, int fn, bool stats) {
+    std::ostringstream o;
+    emit_scene(o, nodes, boxes, fast_bounds, bake);
+    o << "#include \"pt_map_probe.h\"\n";
+    for (const PtProbeKernel &k : kProbeKernels)
+        for (int st = 0; st < 2; ++st)
+            if (fn < 0 || (k.fn == fn && (st != 0) == stats))
+                o << "extern \"C\" __global__ __launch_bounds__(64) void " << k.name << (st ? "_stats" : "")
+                  << "(PtProbe P) {\n  pt::" << k.body << ", " << (st ? "true" : "false") << ">(P);\n}\n";
     return o.str();
 }
 
@@ -797,6 +821,24 @@ extern "C" int pt_scene_kernel_source(const pt_op *ops, uint32_t n_ops, const pt
     std::string src, err;
     const int rc = pt_derive_source(ops, n_ops, aabbs, n_aabb, data, n_data, baked != 0, t, src, err);
     if (rc != PT_OK) return rc;
+    *len = src.size() + 1;
+    if (!out) return PT_OK;
+    if (cap < *len) return PT_ERR_SIZE;
+    std::memcpy(out, src.c_str(), src.size() + 1);
+    return PT_OK;
+}
+
+// The probe module's source for (program, data), as pt_scene_kernel_source
+// returns the scene kernels': the same text up to the kernel list.
+extern "C" int pt_probe_kernel_source(const pt_op *ops, uint32_t n_ops, const pt_aabb *aabbs, uint32_t n_aabb,
+                                      const float *data, uint32_t n_data, int baked, char *out, size_t cap,
+                                      size_t *len) {
+    if ((!ops && n_ops) || (!aabbs && n_aabb) || (!data && n_data) || !len) return PT_ERR_INVALID;
+    PtDerived t;
+    std::string src, err;
+    const int rc = pt_derive_source(ops, n_ops, aabbs, n_aabb, data, n_data, baked != 0, t, src, err);
+    if (rc != PT_OK) return rc;
+    src = pt_probe_source(t.nodes, t.boxes, pt_fast_bounds(t.boxes), baked != 0);
     *len = src.size() + 1;
     if (!out) return PT_OK;
     if (cap < *len) return PT_ERR_SIZE;

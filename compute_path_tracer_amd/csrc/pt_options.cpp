@@ -144,6 +144,9 @@ const Option kOptions[] = {
     // where the scene kernel in use came from: 1 the shipped on-disk cache
     // (lib/jitcache), 0 this process's hipRTC, -1 none loaded
     OPT_READ("jit_cache", c->jit.tier.module ? c->jit.tier_from : (c->jit.mod.module ? c->jit.from : -1)),
+    // the probe modules this context compiled (one per distinct generated source) and their compile seconds
+    OPT_READ("probe_compiles", c->probe.compiles),
+    OPT_READ("probe_seconds", c->probe.seconds),
     OPT_READ("bin_chunks", c->bin.last_chunks),  // of the last timed binned dispatch
     OPT_READ("bin_fallback", c->bin.fallback ? 1.0 : 0.0),
     OPT_READ("bin_bytes", pt_bin_bytes_held(c)),  // (as allocated: the wide buffers stay once a scene needed them)

@@ -165,6 +165,8 @@ int pt_set_data(pt_ctx *c, const float *data, uint32_t n) {
     c->prog.bound_k = pt_bound_k(nodes);
     c->prog.fast_bounds = pt_fast_bounds(boxes);
     pt_jit_refresh(c->jit, nodes, boxes, c->prog.fast_bounds);
+    c->prog.host_nodes = std::move(nodes);
+    c->prog.host_boxes = std::move(boxes);
     return PT_OK;
 }
 
@@ -705,6 +707,7 @@ void pt_destroy(pt_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm.comm) ncclCommDestroy(c->comm.comm);
     pt_jit_destroy(c->jit);  // (waits for a pending tier-up build)
+    pt_probe_unload(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;  // its buffers, events and lane streams go with their owners, on this device
 }

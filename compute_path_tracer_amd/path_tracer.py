@@ -401,6 +401,78 @@ class PathTracer:
                                                               N.ptr(s, ctypes.c_int32)))
         return d, s
 
+    # -- point probes (tests: the scene's map() and bounds() per input) ---------
+    PROBE_KINDS = {"interp": N.PT_PROBE_INTERP, "table": N.PT_PROBE_TABLE, "baked": N.PT_PROBE_BAKED}
+    PROBE_VARIANTS = {"map": N.PT_PROBE_MAP, "b0": N.PT_PROBE_MAP_B0, "b1": N.PT_PROBE_MAP_B1}
+
+    @staticmethod
+    def _probe_in(a, dtype, shape):
+        """An optional input as a contiguous array of `shape` (None stays None)."""
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype).reshape(shape)
+        return a, N.ptr(a, {np.float32: ctypes.c_float, np.uint64: ctypes.c_uint64}[dtype])
+
+    def _probe_counters(self, counters: bool):
+        c = np.zeros(N.PT_STAT_COUNT, np.uint64) if counters else None
+        return c, (N.ptr(c, ctypes.c_uint64) if counters else None)
+
+    @staticmethod
+    def _stat_dict(c):
+        return {name: int(c[k]) for k, name in enumerate(N.STAT_NAMES)}
+
+    def probe_map(self, kind, points, check=None, bnd=None, live_in=None, variant="map", union_mode: int = 0,
+                  counters: bool = False):
+        """pt_probe_map: one map() call per point (float [n][3]) of the
+        interpreter ("interp") or of the scene's generated code ("table",
+        "baked"); ``check`` uint64 [n][2] (None: every bit set), ``bnd`` float
+        [n] (None: +inf), ``live_in`` uint64 [n] (None: 0).  Returns (d float32
+        [n], shape int32 [n], live uint64 [n]), with ``counters`` also the
+        call's work counters by name."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = len(p)
+        ck, ckp = self._probe_in(check, np.uint64, (n, 2))
+        b, bp = self._probe_in(bnd, np.float32, (n,))
+        li, lip = self._probe_in(live_in, np.uint64, (n,))
+        d, s, lo = np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.uint64)
+        c, cp = self._probe_counters(counters)
+        self._chk("pt_probe_map", self._L.pt_probe_map(
+            self._ctx, self.PROBE_KINDS[kind], self.PROBE_VARIANTS[variant], n, N.fptr(p), ckp, bp, lip, int(union_mode),
+            N.fptr(d), N.ptr(s, ctypes.c_int32), N.ptr(lo, ctypes.c_uint64), cp))
+        return (d, s, lo, self._stat_dict(c)) if counters else (d, s, lo)
+
+    def probe_taps(self, kind, hits, check=None, bnd=None, counters: bool = False):
+        """pt_probe_taps: the shade pass's six normal taps around each hit
+        point.  Returns (d6 float32 [n][6], shape6 int32 [n][6], live uint64
+        [n]), with ``counters`` also the work counters."""
+        p = np.ascontiguousarray(hits, np.float32).reshape(-1, 3)
+        n = len(p)
+        ck, ckp = self._probe_in(check, np.uint64, (n, 2))
+        b, bp = self._probe_in(bnd, np.float32, (n,))
+        d, s, lo = np.empty((n, 6), np.float32), np.empty((n, 6), np.int32), np.empty(n, np.uint64)
+        c, cp = self._probe_counters(counters)
+        self._chk("pt_probe_taps", self._L.pt_probe_taps(self._ctx, self.PROBE_KINDS[kind], n, N.fptr(p), ckp, bp,
+                                                          N.fptr(d), N.ptr(s, ctypes.c_int32),
+                                                          N.ptr(lo, ctypes.c_uint64), cp))
+        return (d, s, lo, self._stat_dict(c)) if counters else (d, s, lo)
+
+    def probe_bounds(self, kind, ro, rd, skip_mode: int = 0, counters: bool = False):
+        """pt_probe_bounds: bounds() per ray.  Returns (mask uint64 [n][2]:
+        check[] bits 0..63 and 64..127, skip uint64 [ceil(n / 64)]: each wave's
+        skip word, zeros with skip_mode 0), with ``counters`` also the work counters."""
+        o = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(rd, np.float32).reshape(-1, 3)
+        if len(o) != len(r):
+            raise ValueError("one direction per origin")
+        n = len(o)
+        mask, skip = np.zeros((n, 4), np.uint32), np.zeros((n + 63) // 64, np.uint64)
+        c, cp = self._probe_counters(counters)
+        self._chk("pt_probe_bounds", self._L.pt_probe_bounds(self._ctx, self.PROBE_KINDS[kind], n, N.fptr(o), N.fptr(r),
+                                                              int(skip_mode), N.ptr(mask, ctypes.c_uint32),
+                                                              N.ptr(skip, ctypes.c_uint64), cp))
+        m64 = mask.view(np.uint64).reshape(n, 2)  # (little endian: words 0-1 and 2-3)
+        return (m64, skip, self._stat_dict(c)) if counters else (m64, skip)
+
     def extract_mesh(self, box_min=None, box_max=None, resolution: int = 128, iso: float = 0.0, project: int = 2,
                      grid=None) -> Mesh:
         """pt_mesh_extract + pt_mesh_read: the surface map(p) = ``iso`` inside

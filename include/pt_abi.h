@@ -518,6 +518,61 @@ int pt_check_div_k(int hip_device, float b, uint32_t a0, uint32_t na, uint64_t *
  * and a 64 B record store; ms[k] = device time, bytes[k] = bytes moved. */
 int pt_traffic_probe(int hip_device, uint32_t log2n, float ms[4], uint64_t bytes[4]);
 
+/* Point probes (tests only): the scene's map() and bounds() on
+ * caller-supplied inputs, one thread per input in 64-thread waves, results
+ * per input.  kind: PT_PROBE_INTERP runs the ahead-of-time interpreter
+ * (InterpMap, bounds_mask); PT_PROBE_TABLE / PT_PROBE_BAKED run the scene's own
+ * generated code -- the text of pt_scene_kernel_source up to its kernel list,
+ * values read from the node table / baked as literals -- under probe kernels
+ * in modules of their own (that text and the one kernel a call runs),
+ * compiled with hipRTC at the first call that needs them, once per distinct
+ * source per context (pt_get_option "probe_compiles", "probe_seconds"),
+ * outside the on-disk cache.  The pipeline kernels are not
+ * what runs here: the image tests remain the check of those as compiled.
+ * Blocking.  n = 0 is a no-op.  PT_ERR_INVALID for a NULL context, a missing
+ * input or a value outside the defines; PT_ERR_STATE without program or
+ * data; PT_ERR_HIP when the probe module does not build (pt_jit_log has the
+ * compile log).  Every lane of a wave takes part in the wave-level steps; the
+ * lanes beyond n carry an empty mask.  counters (PT_STAT_COUNT words, may be
+ * NULL): the call's work counters, as pt_dispatch_stats counts; with
+ * counters the instrumented build of the same code runs. */
+#define PT_PROBE_INTERP 0
+#define PT_PROBE_TABLE 1
+#define PT_PROBE_BAKED 2
+#define PT_PROBE_MAP 0     /* JitMap: the march steps' map() */
+#define PT_PROBE_MAP_B0 1  /* JitMapB0: the shade pass's first tap (bound rule, records `live`) */
+#define PT_PROBE_MAP_B1 2  /* JitMapB1: its other five taps (evaluates what `live` names) */
+/* One map() call per point.  check: [n][2] check[] bits 0..63 and 64..127
+ * (NULL: every bit set); bnd: [n] the map() bound of the B variants (NULL:
+ * +inf; NaN: rule off), widened about the point itself as the shade pass
+ * widens it about the hit; live_in: [n] (NULL: 0).  union_mode 0: the wave's
+ * union of masks is "no information" (all ones); 1: the OR of the wave's
+ * masks, as the trace pass forms it.  d, shape (as pt_sample_field's) and
+ * live_out may each be NULL.  A point with a non-finite coordinate is mapped as
+ * (NaN, NaN, NaN), as pt_sample_field maps it. */
+int pt_probe_map(pt_ctx *ctx, int kind, int variant, uint32_t n, const float *xyz, const uint64_t *check,
+                 const float *bnd, const uint64_t *live_in, int union_mode, float *d, int32_t *shape,
+                 uint64_t *live_out, uint64_t *counters);
+/* The shade pass's six normal taps around each hit point, in its order (+x,
+ * -x, +y, -y, +z, -z at 1e-4): d6 / shape6 [n][6], live [n] = the live mask
+ * the first tap recorded.  Each output may be NULL. */
+int pt_probe_taps(pt_ctx *ctx, int kind, uint32_t n, const float *hit, const uint64_t *check, const float *bnd,
+                  float *d6, int32_t *shape6, uint64_t *live, uint64_t *counters);
+/* bounds() per ray: mask [n][4], check[] bit k = word k / 32, bit k % 32.
+ * skip_mode 1: each full wave of 64 rays first asks which boxes none of its
+ * rays can hit (the first pass's primary_box_skip) and leaves those out;
+ * skip [ceil(n / 64)] = that word per wave (0 for a ragged wave; may be NULL). */
+int pt_probe_bounds(pt_ctx *ctx, int kind, uint32_t n, const float *ro, const float *rd, int skip_mode,
+                    uint32_t *mask, uint64_t *skip, uint64_t *counters);
+/* The probe module's source for (program, data), as pt_scene_kernel_source
+ * returns the scene kernels' (host only, same two-call pattern). */
+int pt_probe_kernel_source(const pt_op *ops, uint32_t n_ops, const pt_aabb *aabbs, uint32_t n_aabb,
+                           const float *data, uint32_t n_data, int baked, char *out, size_t cap, size_t *len);
+/* Build that source as pt_probe_map builds it, without a device (validation):
+ * log = the compile log, *code_bytes = code object size. */
+int pt_probe_jit_compile(const pt_op *ops, uint32_t n_ops, const pt_aabb *aabbs, uint32_t n_aabb, const float *data,
+                         uint32_t n_data, int baked, char *log, size_t log_cap, size_t *code_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,37 @@ class OracleScene:
         return image
 
 
+class Segment(Structure):
+    """pto_segment: one logged path segment (its ray, its bounds() mask as
+    check[] bits 0..63 and 64..127, its index in the path, march steps, hit)."""
+
+    _fields_ = [("ro", c_float * 3), ("rd", c_float * 3), ("mask", c_uint64 * 2), ("seg", c_int32),
+                ("steps", c_int32), ("hit", c_int32), ("pad", c_int32)]
+
+
+def logged_segments(scene: OracleScene, width: int, height: int, spp: int, bounces: int, cap: int = 20000):
+    """Every path segment of a single-threaded render of frame 1 with counters
+    (pto_set_segment_log), in the order the oracle traced them: (ro float32
+    [n][3], rd float32 [n][3], mask uint64 [n][2], seg, steps, hit int32 [n])."""
+    L = lib()
+    L.pto_set_segment_log.argtypes = [c_void_p, c_int]
+    L.pto_set_segment_log.restype = None
+    L.pto_segment_log_count.restype = c_int
+    buf = (Segment * cap)()
+    L.pto_set_segment_log(ctypes.cast(buf, c_void_p), cap)
+    try:
+        aspect = float(np.float32(width) / np.float32(height))
+        scene.render(width, height, Constants(0.0, 1, aspect, 1), Settings(0, bounces, 1.0, 1.0, 0), spp, threads=1,
+                     counters=True)
+        n = L.pto_segment_log_count()
+    finally:
+        L.pto_set_segment_log(None, 0)
+    raw = np.frombuffer(buf, dtype=np.dtype([("ro", np.float32, 3), ("rd", np.float32, 3), ("mask", np.uint64, 2),
+                                             ("seg", np.int32), ("steps", np.int32), ("hit", np.int32),
+                                             ("pad", np.int32)]), count=n).copy()
+    return raw["ro"], raw["rd"], raw["mask"], raw["seg"], raw["steps"], raw["hit"]
+
+
 def wang_hash(seed: int) -> int:
     s = c_uint32(seed)
     return int(lib().pto_wang_hash(ctypes.byref(s)))

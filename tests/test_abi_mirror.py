@@ -60,9 +60,11 @@ def test_parser_reads_declarator_lists():
 
 def test_defines():
     defines = header_defines()
-    assert len(defines) >= 40 and defines["PT_ERR_SIZE"] == -6 and defines["PT_NODE_FLOATS"] == 29
+    assert len(defines) >= 46 and defines["PT_ERR_SIZE"] == -6 and defines["PT_NODE_FLOATS"] == 29
     mirrored = {k: v for k, v in vars(N).items() if k.startswith("PT_") and isinstance(v, int)}
-    assert len(mirrored) >= 35
+    assert len(mirrored) >= 41
+    assert (defines["PT_PROBE_INTERP"], defines["PT_PROBE_TABLE"], defines["PT_PROBE_BAKED"]) == (0, 1, 2)
+    assert (defines["PT_PROBE_MAP"], defines["PT_PROBE_MAP_B0"], defines["PT_PROBE_MAP_B1"]) == (0, 1, 2)
     for name, val in defines.items():
         if name in mirrored:
             assert mirrored[name] == val, name
@@ -85,7 +87,8 @@ def test_struct_fields(name):
 
 def test_signature_table_names_the_declared_functions():
     declared = set(re.findall(r"\b(pt_[a-z0-9_]+)\s*\(", header()))
-    assert len(declared) >= 20
+    assert len(declared) >= 56
+    assert {"pt_probe_map", "pt_probe_taps", "pt_probe_bounds", "pt_probe_kernel_source", "pt_probe_jit_compile"} <= declared
     assert set(N.SIGNATURES) == declared
     assert N.SYMBOLS == tuple(N.SIGNATURES)
     for name, (restype, argtypes) in N.SIGNATURES.items():

@@ -4,8 +4,10 @@ The bound data (PtNode.pad[0], pt_derive.cpp pt_cull_bounds) is read back
 from the values-baked hipRTC source (exact hex literals) and recomputed here
 from the same baked node values; the generated map() must carry the parent
 rule exactly for the unions the rule allows.  No GPU: hipRTC cross-compiles.
-The exactness of the culled images is checked on the GPU by
-test_gpu_parity.py (scene "cull" and every scene with eligible unions)."""
+The numerics -- every map() variant and bounds() against the oracle, point by
+point -- are checked on the GPU by test_gpu_map.py; the
+exactness of the culled images by test_gpu_parity.py (scene "cull" and every
+scene with eligible unions)."""
 import ctypes
 import math
 import os
