@@ -90,6 +90,13 @@ class GuidedParams(Structure):
                 ("sigma_depth", c_float), ("sigma_albedo", c_float)]
 
 
+class TemporalParams(Structure):
+    """pt_temporal_params: the history cap and the reprojection tests of ``pt_temporal_accumulate`` (new)."""
+
+    _fields_ = [("max_history", c_float), ("depth_tolerance", c_float), ("normal_cos", c_float),
+                ("albedo_tolerance", c_float)]
+
+
 PT_MESH_BRICK, PT_MESH_MAX_CELLS, PT_MESH_MAX_PROJECT = 8, 1024, 8
 
 
@@ -144,7 +151,7 @@ class Aabb(Structure):
 
 assert ctypes.sizeof(Constants) == 16 and ctypes.sizeof(Settings) == 20
 assert ctypes.sizeof(Camera) == 56 and ctypes.sizeof(Sky) == 52 and ctypes.sizeof(DenoiseParams) == 20
-assert ctypes.sizeof(GuidedParams) == 20
+assert ctypes.sizeof(GuidedParams) == 20 and ctypes.sizeof(TemporalParams) == 16
 assert ctypes.sizeof(MeshDesc) == 36 and ctypes.sizeof(MeshInfo) == 48
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
@@ -207,6 +214,10 @@ SIGNATURES = {
     "pt_write_moments": (c_int, [_ctx, _f32p, c_size_t, c_uint32]),
     "pt_read_variance": (c_int, [_ctx, _f32p, c_size_t]),
     "pt_denoise_guided": (c_int, [_ctx, POINTER(GuidedParams), c_int, c_void_p, c_size_t]),
+    "pt_temporal_accumulate": (c_int, [_ctx, POINTER(TemporalParams)]),
+    "pt_temporal_reset": (c_int, [_ctx]),
+    "pt_read_history": (c_int, [_ctx, _f32p, _f32p, _f32p, c_size_t]),
+    "pt_denoise_history": (c_int, [_ctx, POINTER(GuidedParams), c_int, c_void_p, c_size_t]),
     "pt_sample_field": (c_int, [_ctx, _f32p, c_uint32, _f32p, POINTER(c_int32)]),
     "pt_mesh_extract": (c_int, [_ctx, POINTER(MeshDesc), POINTER(MeshInfo)]),
     "pt_mesh_read": (c_int, [_ctx, _f32p, _f32p, POINTER(c_int32), _u32p, c_size_t, c_size_t]),

@@ -184,7 +184,31 @@ struct pt_ctx {
         bool guides_valid = false;
         int lds = 1;  // pt_set_option "denoise_lds": LDS-staged taps at steps 1 and 2 (-19 % on five iterations: EXPERIMENTS.md)
         TimedSection guide_time, denoise_time;
+        // the view the guides were rendered with (pt_temporal_accumulate projects through it): a lens as its pinhole
+        int guide_cam_mode = PT_CAM_DEFAULT;
+        pt_camera guide_cam = kDefaultCamera;
+        float guide_aspect = 1.0f, guide_fov = 1.0f;
     } dn;
+    // temporal accumulation (pt_temporal_accumulate): two sets of history images -- colour and
+    // second moment (16 B/px each), sample count (4 B/px), a copy of the guide planes (16 B/px each) -- of which
+    // set[cur] is the history and the other the next accumulate's target, allocated at the first accumulate; the
+    // view the history is seen from; the accumulates since it was last dropped; the timing of its kernels
+    struct History {
+        struct Set {
+            DevBuf h, hm, hn, g0, g1;
+        } set[2];
+        int cur = 0;
+        bool valid = false;
+        uint32_t views = 0;
+        int cam_mode = PT_CAM_DEFAULT;
+        pt_camera cam = kDefaultCamera;
+        float aspect = 1.0f, fov = 1.0f;
+        TimedSection accumulate_time, variance_time, denoise_time;
+        void drop() {
+            valid = false;
+            views = 0;
+        }
+    } hist;
     // second moments (pt_set_option "moments"): the image M of each frame's squared colour,
     // mixed as the accumulation image is (16 B/px, held while the option is on); whether it and the
     // accumulation image are one render's, and of how many frames; the variance plane's two ping-pong

@@ -61,6 +61,28 @@ struct PtGuided {
     float kz[PT_DENOISE_MAX_ITERATIONS];
 };
 void pt_launch_guided(const PtGuided &A, bool lds, hipStream_t stream);  // lds: staged taps at steps 1 and 2
+// temporal accumulation (pt_temporal_accumulate): the current view -- image, moments, guides, of
+// n_cur frames, under (cam_mode, cam, aspect, fov) -- merged with the history of the previous view (p*: its colour,
+// moments, count and guide planes, its camera, and that camera's origin and reciprocal basis) into the new history
+// (o*).  have 0: nothing is taken and no p* pointer is read (no history yet, or a degenerate previous basis)
+struct PtTemporal {
+    const float4 *a, *m, *g0, *g1;
+    const float4 *ph, *phm, *pg0, *pg1;
+    const float *phn;
+    float4 *oh, *ohm;
+    float *ohn;
+    int32_t w, h;
+    int32_t have;
+    int32_t cam_mode, pcam_mode;  // PT_CAM_DEFAULT or PT_CAM_PINHOLE (a lens as its pinhole)
+    float n_cur;
+    float aspect, fov, paspect, pfov;
+    float max_history, depth_tolerance, normal_cos, at2;  // at2 = albedo_tolerance squared
+    float po[3], ir[3], iu[3], ifw[3];
+    pt_camera cam, pcam;
+};
+void pt_launch_temporal(const PtTemporal &T, hipStream_t stream);
+// v[i] as pt_launch_variance with a count per texel: v.k = max(HM.k - H.k * H.k, 0) / (HN - 1) (pt_denoise_history)
+void pt_launch_history_variance(const float *h, const float *hm, const float *hn, float *v, uint32_t n, hipStream_t stream);
 
 // Expand (program, data[]) into the device tables (see pt_device.h).
 int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, const float *data, uint32_t n,

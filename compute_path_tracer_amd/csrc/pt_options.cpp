@@ -177,6 +177,13 @@ const Option kOptions[] = {
     OPT_READ("moment_frames", c->mom.valid ? c->mom.frames : 0u),
     OPT_GET("variance_ms", section_ms(c, c->mom.variance_time, true, v)),
     OPT_GET("guided_ms", section_ms(c, c->mom.guided_time, true, v)),
+    // temporal accumulation: whether the context holds a history, and of how many accumulates; the last
+    // pt_temporal_accumulate's kernel; the last pt_denoise_history's variance kernel and all its iterations
+    OPT_READ("history_valid", c->hist.valid ? 1.0 : 0.0),
+    OPT_READ("history_views", c->hist.views),
+    OPT_GET("temporal_ms", section_ms(c, c->hist.accumulate_time, true, v)),
+    OPT_GET("history_variance_ms", section_ms(c, c->hist.variance_time, true, v)),
+    OPT_GET("history_denoise_ms", section_ms(c, c->hist.denoise_time, true, v)),
     OPT_GET("tap_stat_", tap_stat(c, key_, v)),
 };
 

@@ -28,6 +28,7 @@ static_assert(sizeof(pt_camera) == 14 * 4, "pt_camera layout");
 static_assert(sizeof(pt_sky) == 13 * 4, "pt_sky layout");
 static_assert(sizeof(pt_denoise_params) == 5 * 4, "pt_denoise_params layout");
 static_assert(sizeof(pt_guided_params) == 5 * 4, "pt_guided_params layout");
+static_assert(sizeof(pt_temporal_params) == 4 * 4, "pt_temporal_params layout");
 
 static int alloc_image(pt_ctx *c, uint32_t w, uint32_t h) {
     c->img.accum.release();
@@ -96,6 +97,7 @@ static int resize_clear(pt_ctx *c, uint32_t width, uint32_t height) {
 int pt_resize_clear(pt_ctx *c, uint32_t width, uint32_t height) {
     if (!c) return PT_ERR_INVALID;
     c->dn.guides_valid = false;
+    if (width != c->img.width || height != c->img.height) c->hist.drop();  // (at the same size it is a clear: the history stays)
     return resize_clear(c, width, height);
 }
 
@@ -129,6 +131,7 @@ int pt_set_program(pt_ctx *c, const pt_op *ops, uint32_t n_ops, const pt_aabb *a
         if (aabbs[i].back < 0 || aabbs[i].back >= int32_t(n_check) || aabbs[i].so_kind > PT_SO_TORUS)
             return fail(c, PT_ERR_INVALID, "bad aabb record");
     c->dn.guides_valid = false;
+    c->hist.drop();
     c->prog.ops.assign(ops, ops + n_ops);
     c->prog.aabbs.assign(aabbs, aabbs + n_aabb);
     c->prog.n_check = n_check;
@@ -148,6 +151,7 @@ int pt_set_data(pt_ctx *c, const float *data, uint32_t n) {
     int rc = pt_derive(c->prog.ops, c->prog.aabbs, data, n, nodes, boxes, mats, err);
     if (rc != PT_OK) return fail(c, rc, err);
     c->dn.guides_valid = false;
+    c->hist.drop();
     HIPCHK(c, hipSetDevice(c->device));
     // stream-ordered upload: in-flight dispatches finish with the old tables
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -469,6 +473,10 @@ int pt_render_guides(pt_ctx *c, const pt_constants *k, const pt_settings *s) {
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, c->dn.guide_time.end(c->stream));
     c->dn.guides_valid = true;
+    c->dn.guide_cam_mode = L.cam_mode;  // the view of these guides (pt_temporal_accumulate)
+    c->dn.guide_cam = L.cam;
+    c->dn.guide_aspect = L.aspect;
+    c->dn.guide_fov = L.fov;
     return PT_OK;
 }
 
@@ -606,6 +614,200 @@ int pt_denoise_guided(pt_ctx *c, const pt_guided_params *p, int format, void *ou
         src = c->dn.filter[i & 1].as<float>();
     }
     HIPCHK(c, c->mom.guided_time.end(c->stream));
+    const void *result = src;
+    if (format != PT_DENOISE_LINEAR) {
+        pt_launch_display(src, c->img.width, c->img.height, format, c->img.display.p, c->stream);
+        HIPCHK(c, hipGetLastError());
+        result = c->img.display.p;
+    }
+    return read_back(c, out, bytes, result, need, nullptr);
+}
+
+// ---- temporal accumulation ---------------------------------------
+// The reciprocal basis of (right, up, forward): cross products over the determinant, in double, each component
+// rounded once to f32.  false: the determinant is zero or not finite (nothing can be projected).
+static bool reciprocal_basis(const pt_camera &cam, float ir[3], float iu[3], float ifw[3]) {
+    const double r[3] = {cam.right[0], cam.right[1], cam.right[2]}, u[3] = {cam.up[0], cam.up[1], cam.up[2]},
+                 f[3] = {cam.forward[0], cam.forward[1], cam.forward[2]};
+    auto cross = [](const double a[3], const double b[3], double o[3]) {
+        o[0] = a[1] * b[2] - a[2] * b[1];
+        o[1] = a[2] * b[0] - a[0] * b[2];
+        o[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    double uf[3], fr[3], ru[3];
+    cross(u, f, uf);
+    cross(f, r, fr);
+    cross(r, u, ru);
+    const double det = (r[0] * uf[0] + r[1] * uf[1]) + r[2] * uf[2];
+    if (!std::isfinite(det) || det == 0.0) return false;
+    for (int k = 0; k < 3; ++k) {
+        ir[k] = float(uf[k] / det);
+        iu[k] = float(fr[k] / det);
+        ifw[k] = float(ru[k] / det);
+    }
+    return true;
+}
+
+static const char *const kNoHistory = "no history: call pt_temporal_accumulate";
+
+int pt_temporal_accumulate(pt_ctx *c, const pt_temporal_params *p) {
+    if (!c) return PT_ERR_INVALID;
+    if (!p) return fail(c, PT_ERR_INVALID, "null temporal parameters");
+    for (float v : {p->max_history, p->depth_tolerance, p->albedo_tolerance})
+        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "temporal max_history and tolerances must be finite and >= 0");
+    if (!(p->normal_cos >= -1.0f && p->normal_cos <= 1.0f)) return fail(c, PT_ERR_INVALID, "temporal normal_cos must lie in [-1, 1]");
+    if (c->view.nranks != 1)
+        return fail(c, PT_ERR_UNSUPPORTED, "the history is of the whole image: pt_set_tiles(0, 1), then write the reduced image and moments");
+    if (!c->dn.guides_valid) return fail(c, PT_ERR_STATE, "guides stale: call pt_render_guides");
+    if (!c->mom.valid || c->mom.frames < 2) return fail(c, PT_ERR_STATE, kNoVariance);
+    HIPCHK(c, hipSetDevice(c->device));
+    pt_ctx::History &hs = c->hist;
+    const size_t texels = size_t(c->img.width) * c->img.height;
+    const size_t rgba = std::max<size_t>(texels * 16, 16), plane = std::max<size_t>(texels * sizeof(float), 16);
+    int rc;
+    for (pt_ctx::History::Set &s : hs.set) {
+        for (DevBuf *b : {&s.h, &s.hm, &s.g0, &s.g1})
+            if ((rc = ensure(c, *b, rgba)) != PT_OK) return rc;
+        if ((rc = ensure(c, s.hn, plane)) != PT_OK) return rc;
+    }
+    const pt_ctx::History::Set &prev = hs.set[hs.cur], &next = hs.set[hs.cur ^ 1];
+    PtTemporal T;
+    std::memset(&T, 0, sizeof T);
+    T.a = c->img.accum.as<const float4>();
+    T.m = c->mom.img.as<const float4>();
+    T.g0 = c->dn.guides[0].as<const float4>();
+    T.g1 = c->dn.guides[1].as<const float4>();
+    T.ph = prev.h.as<const float4>();
+    T.phm = prev.hm.as<const float4>();
+    T.phn = prev.hn.as<const float>();
+    T.pg0 = prev.g0.as<const float4>();
+    T.pg1 = prev.g1.as<const float4>();
+    T.oh = next.h.as<float4>();
+    T.ohm = next.hm.as<float4>();
+    T.ohn = next.hn.as<float>();
+    T.w = int32_t(c->img.width);
+    T.h = int32_t(c->img.height);
+    T.n_cur = float(c->mom.frames);
+    T.cam_mode = c->dn.guide_cam_mode;
+    T.cam = c->dn.guide_cam;
+    T.aspect = c->dn.guide_aspect;
+    T.fov = c->dn.guide_fov;
+    T.pcam_mode = hs.cam_mode;
+    T.pcam = hs.cam;
+    T.paspect = hs.aspect;
+    T.pfov = hs.fov;
+    T.max_history = p->max_history;
+    T.depth_tolerance = p->depth_tolerance;
+    T.normal_cos = p->normal_cos;
+    T.at2 = p->albedo_tolerance * p->albedo_tolerance;
+    for (int k = 0; k < 3; ++k) T.po[k] = hs.cam.origin[k];
+    // (a degenerate previous basis: nothing is taken, the history starts again from the current view)
+    T.have = hs.valid && reciprocal_basis(hs.cam, T.ir, T.iu, T.ifw) ? 1 : 0;
+    HIPCHK(c, hs.accumulate_time.begin(c->stream));
+    pt_launch_temporal(T, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hs.accumulate_time.end(c->stream));
+    // the new history's guides are the current view's
+    if (texels) {
+        HIPCHK(c, hipMemcpyAsync(next.g0.p, c->dn.guides[0].p, texels * 16, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(next.g1.p, c->dn.guides[1].p, texels * 16, hipMemcpyDeviceToDevice, c->stream));
+    }
+    hs.cur ^= 1;
+    hs.cam_mode = T.cam_mode;
+    hs.cam = T.cam;
+    hs.aspect = T.aspect;
+    hs.fov = T.fov;
+    hs.valid = true;
+    hs.views += 1;
+    return PT_OK;
+}
+
+int pt_temporal_reset(pt_ctx *c) {
+    if (!c) return PT_ERR_INVALID;
+    c->hist.drop();
+    return PT_OK;
+}
+
+int pt_read_history(pt_ctx *c, float *colour, float *moments, float *count, size_t bytes_rgba) {
+    if (!c) return PT_ERR_INVALID;
+    if (!c->hist.valid) return fail(c, PT_ERR_STATE, kNoHistory);
+    const size_t need = c->img.bytes();
+    if (bytes_rgba < need) return fail(c, PT_ERR_SIZE, "history buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    const pt_ctx::History::Set &s = c->hist.set[c->hist.cur];
+    // (any of the three may be left out; one wait for all)
+    if (colour && need) HIPCHK(c, hipMemcpyAsync(colour, s.h.p, need, hipMemcpyDeviceToHost, c->stream));
+    if (moments && need) HIPCHK(c, hipMemcpyAsync(moments, s.hm.p, need, hipMemcpyDeviceToHost, c->stream));
+    return read_back(c, count, need / 4, s.hn.p, count ? need / 4 : 0, nullptr);
+}
+
+// pt_denoise_guided over the history: its checks in its order, the history for its two state
+// rules, the history's colour, guides and per-pixel count for the accumulation image, the live guides and n.
+int pt_denoise_history(pt_ctx *c, const pt_guided_params *p, int format, void *out, size_t bytes) {
+    if (!c) return PT_ERR_INVALID;
+    if (!p) return fail(c, PT_ERR_INVALID, "null denoise parameters");
+    if (format != PT_DISPLAY_RGBA32F && format != PT_DISPLAY_SRGB8 && format != PT_DENOISE_LINEAR)
+        return fail(c, PT_ERR_INVALID, "bad denoise format");
+    if (p->iterations < 1 || p->iterations > PT_DENOISE_MAX_ITERATIONS)
+        return fail(c, PT_ERR_INVALID, "denoise iterations must be in [1, 8]");
+    if (p->normal_power_log2 > 8) return fail(c, PT_ERR_INVALID, "denoise normal_power_log2 must be in [0, 8]");
+    for (float v : {p->sigma_depth, p->sigma_albedo})
+        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "denoise sigma must be finite and >= 0");
+    if (!std::isfinite(p->sigma_variance) || !(p->sigma_variance > 0.0f))
+        return fail(c, PT_ERR_INVALID, "denoise sigma_variance must be finite and > 0");
+    PtGuided A;
+    std::memset(&A, 0, sizeof A);
+    auto inv_sq = [](float sigma, float scale) {  // (as pt_denoise)
+        if (sigma == 0.0f) return 0.0f;
+        const float v = sigma * scale;
+        const float sq = v * v;
+        return 1.0f / sq;
+    };
+    A.ka = inv_sq(p->sigma_albedo, 1.0f);
+    bool finite = std::isfinite(A.ka);
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        A.kz[i] = inv_sq(p->sigma_depth, std::ldexp(1.0f, int(i)));
+        finite = finite && std::isfinite(A.kz[i]);
+    }
+    if (!finite) return fail(c, PT_ERR_INVALID, "denoise sigma too small: 1 / sigma^2 is not finite");
+    A.sv2 = p->sigma_variance * p->sigma_variance;
+    if (!c->hist.valid) return fail(c, PT_ERR_STATE, kNoHistory);
+    const size_t texels = size_t(c->img.width) * c->img.height;
+    const size_t need = texels * (format == PT_DISPLAY_SRGB8 ? 4 : 16);
+    if (!out || bytes < need) return fail(c, PT_ERR_SIZE, "denoise output buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    for (DevBuf &f : c->dn.filter)
+        if ((rc = ensure(c, f, std::max<size_t>(texels * 16, 16))) != PT_OK) return rc;
+    for (DevBuf &v : c->mom.var)
+        if ((rc = ensure(c, v, std::max<size_t>(texels * sizeof(float), 16))) != PT_OK) return rc;
+    if (format != PT_DENOISE_LINEAR && (rc = ensure(c, c->img.display, std::max<size_t>(need, 16))) != PT_OK) return rc;
+    pt_ctx::History &hs = c->hist;
+    const pt_ctx::History::Set &s = hs.set[hs.cur];
+    HIPCHK(c, hs.variance_time.begin(c->stream));
+    pt_launch_history_variance(s.h.as<float>(), s.hm.as<float>(), s.hn.as<float>(), c->mom.var[0].as<float>(), uint32_t(texels),
+                               c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hs.variance_time.end(c->stream));
+    A.g0 = s.g0.as<const float4>();
+    A.g1 = s.g1.as<const float4>();
+    A.w = int32_t(c->img.width);
+    A.h = int32_t(c->img.height);
+    A.npow = int32_t(p->normal_power_log2);
+    // history colour -> filter[0] -> filter[1] ..., variance var[0] -> var[1] -> var[0] ...: the history is only read
+    const float *src = s.h.as<float>();
+    HIPCHK(c, hs.denoise_time.begin(c->stream));
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        A.in = reinterpret_cast<const float4 *>(src);
+        A.out = c->dn.filter[i & 1].as<float4>();
+        A.vin = c->mom.var[i & 1].as<const float>();
+        A.vout = c->mom.var[(i + 1) & 1].as<float>();
+        A.iter = int32_t(i);
+        pt_launch_guided(A, c->dn.lds != 0, c->stream);
+        HIPCHK(c, hipGetLastError());
+        src = c->dn.filter[i & 1].as<float>();
+    }
+    HIPCHK(c, hs.denoise_time.end(c->stream));
     const void *result = src;
     if (format != PT_DENOISE_LINEAR) {
         pt_launch_display(src, c->img.width, c->img.height, format, c->img.display.p, c->stream);

@@ -389,6 +389,76 @@ class PathTracer:
         self.constants.last_clear = done - 1  # render()'s next frame mixes with last_clear = done
         return done
 
+    # -- temporal accumulation (new: a history reprojected across camera moves) --
+    def accumulate_history(self, max_history: float = 16.0, depth_tolerance: float = 0.05, normal_cos: float = 0.9,
+                           albedo_tolerance: float = 0.1) -> None:
+        """pt_temporal_accumulate: merge the current view -- the image, its
+        moments (>= 2 frames) and the guides of ``render_guides`` -- into the
+        context's history.  Each hit pixel's first-hit point is projected into
+        the view of the last accumulate and takes, bilinearly, the history
+        texels there that show the same surface (within ``depth_tolerance``
+        of its tangent plane as a share of the distance, normals agreeing to
+        ``normal_cos``, albedo to ``albedo_tolerance``), weighing at most
+        ``max_history`` samples; a pixel that finds none starts again.  The
+        image, moments and guides are left as they are.  A camera move keeps
+        the history; a scene change or a resize drops it, and a change of the
+        light wants ``reset_history``."""
+        p = N.TemporalParams(max_history=float(max_history), depth_tolerance=float(depth_tolerance),
+                             normal_cos=float(normal_cos), albedo_tolerance=float(albedo_tolerance))
+        self._chk("pt_temporal_accumulate", self._L.pt_temporal_accumulate(self._ctx, ctypes.byref(p)))
+
+    def reset_history(self) -> None:
+        """pt_temporal_reset: drop the history; the next accumulate starts it from its view."""
+        self._chk("pt_temporal_reset", self._L.pt_temporal_reset(self._ctx))
+
+    def read_history(self):
+        """pt_read_history: (colour, moments, count) -- float32 [height][width][4]
+        twice, rows as read_image, and the samples per pixel, float32 [height][width]."""
+        (hc, pc, nbytes), (hm, pm, _) = self._image(), self._image()
+        w, h = self.size
+        hn = np.empty((h, w), np.float32)
+        self._chk("pt_read_history", self._L.pt_read_history(self._ctx, pc, pm, N.fptr(hn), nbytes))
+        return hc, hm, hn
+
+    def denoise_history(self, iterations: int = 5, sigma_variance: float = 2.0, sigma_depth: float = 0.05,
+                        sigma_albedo: float = 0.1, normal_power_log2: int = 5, output: str = "linear") -> np.ndarray:
+        """pt_denoise_history: ``denoise_guided`` over the history -- its
+        colour, the variance of its moments and per-pixel sample count, and
+        its own copy of the guides, so it works after a camera move has made
+        the live guides stale.  ``output`` as ``denoise``."""
+        if output not in self.DENOISE_OUTPUTS:
+            raise ValueError(f"output must be one of {sorted(self.DENOISE_OUTPUTS)}, got {output!r}")
+        p = N.GuidedParams(iterations=int(iterations), normal_power_log2=int(normal_power_log2),
+                           sigma_variance=float(sigma_variance), sigma_depth=float(sigma_depth),
+                           sigma_albedo=float(sigma_albedo))
+        out, po, nbytes = self._image(np.uint8 if output == "srgb8" else np.float32)
+        self._chk("pt_denoise_history", self._L.pt_denoise_history(self._ctx, ctypes.byref(p),
+                                                                    self.DENOISE_OUTPUTS[output], po, nbytes))
+        return out
+
+    def render_view(self, spp: int, camera: Optional[N.Camera] = None, **accumulate) -> None:
+        """One view of an interactive loop in one call: set ``camera`` if one
+        is given, clear the image, switch ``moments`` on, render ``spp`` (>= 2)
+        frames as a plain running mean (the first frame's last_clear is 0),
+        ``render_guides``, ``accumulate_history(**accumulate)``.  The frame
+        counter goes on, so successive views draw distinct samples;
+        ``read_history`` / ``denoise_history`` show the result."""
+        if spp < 2:
+            raise ValueError("render_view needs spp >= 2 (the moments of one frame have no variance)")
+        if camera is not None:
+            self._set_camera(camera)
+        self.clear()
+        self.changed = False
+        self.set_option("moments", 1)
+        c = self._constants(1)
+        c.last_clear = 0
+        self.constants.aspect = c.aspect
+        self.dispatch(c, spp)
+        self.constants.frame += spp
+        self.constants.last_clear = spp - 1  # render()'s next frame mixes with last_clear = spp
+        self.render_guides()
+        self.accumulate_history(**accumulate)
+
     # -- mesh export (new: field sampling and a surface-nets extractor) -------
     def sample_field(self, points):
         """pt_sample_field: map() at ``points`` (float [n][3]) with every

@@ -362,6 +362,56 @@ typedef struct pt_guided_params { /* 20 bytes */
  * PT_ERR_STATE without valid moments of n >= 2 frames and PT_ERR_INVALID for
  * a sigma_variance that is not finite or <= 0.  Reads A and M, writes neither. */
 int pt_denoise_guided(pt_ctx *ctx, const pt_guided_params *p, int format, void *out, size_t bytes);
+/* Temporal accumulation with reprojection (new; DESIGN.md 3.30 has the f32
+ * steps).  A context keeps a history of its own size: colour H and second
+ * moment HM (RGBA32F), a sample count HN per pixel (f32), and a copy of the
+ * guide planes with the camera, aspect and fov they were rendered with --
+ * what has been accumulated, seen from the view of the last accumulate.
+ * pt_temporal_accumulate merges the current view into it: the image A and its
+ * moments M (valid, n >= 2 frames) with the valid guides of pt_render_guides.
+ * A hit pixel's first-hit point is projected into the history's view; the four
+ * history texels around it are gathered bilinearly, each one only if it is a
+ * hit with a finite history whose own first-hit point lies within
+ * depth_tolerance * (the point's distance to the previous eye) of the pixel's
+ * tangent plane, whose normal agrees (dot >= normal_cos) and whose albedo is
+ * within albedo_tolerance.  What is gathered counts as min(its samples,
+ * max_history) samples beside the n of the current view; a pixel that gathers
+ * nothing starts again from the current view.  The result is the new history,
+ * in the current view. */
+typedef struct pt_temporal_params { /* 16 bytes */
+    float max_history;        /* finite, >= 0: the most samples a pixel's history may weigh; 0 = history ignored */
+    float depth_tolerance;    /* finite, >= 0: plane distance allowed, as a share of the point's distance to the previous eye */
+    float normal_cos;         /* in [-1, 1] */
+    float albedo_tolerance;   /* finite, >= 0 */
+} pt_temporal_params;
+/* Asynchronous, on the context's stream; reads A, M and the guides and writes
+ * none of them (a render goes on afterwards as if it had not been called).
+ * The first call, and the first after the history was dropped, makes the
+ * history a copy of the current view.  The history's buffers (two sets: the
+ * kernel gathers from one while it writes the other) are allocated at the
+ * first call.  PT_ERR_INVALID for a NULL or out-of-range parameter;
+ * PT_ERR_UNSUPPORTED while pt_set_tiles leaves the context part of the image
+ * (a multi-rank render writes its reduced image and moments into a context
+ * first, as for the denoisers); PT_ERR_STATE without valid guides or without
+ * valid moments of n >= 2 frames.  A refused call leaves the history as it
+ * was.  pt_temporal_reset, pt_set_program, pt_set_data and a pt_resize_clear
+ * to another size drop the history; pt_set_camera, pt_set_sky, pt_set_tiles,
+ * option and settings changes, dispatches and a pt_resize_clear at the same
+ * size (a clear) do not: a caller who changes the light follows it with
+ * pt_temporal_reset, as they follow it with a clear. */
+int pt_temporal_accumulate(pt_ctx *ctx, const pt_temporal_params *p);
+int pt_temporal_reset(pt_ctx *ctx);
+/* Blocking copy of the history: colour and moments w*h*4 floats each
+ * (bytes_rgba bytes at least), count w*h floats.  Any pointer may be NULL.
+ * PT_ERR_STATE without a history. */
+int pt_read_history(pt_ctx *ctx, float *colour, float *moments, float *count, size_t bytes_rgba);
+/* pt_denoise_guided's filter over the history: the colour source is H, the
+ * guides are the history's own copy (so it works after pt_set_camera has
+ * invalidated the live ones), and the variance plane is
+ *   v.k = max(HM.k - H.k * H.k, 0) / (HN - 1), V = (v.r + v.g) + v.b.
+ * Formats, sizes, parameters and refusals as pt_denoise_guided, with
+ * PT_ERR_STATE for "no history" in place of its two state rules. */
+int pt_denoise_history(pt_ctx *ctx, const pt_guided_params *p, int format, void *out, size_t bytes);
 /* Mesh export (new; DESIGN.md 3.27 has the f32 steps and the orders).
  * Field sampling: map() at n caller points (xyz, 3 floats each) with every
  * check[] entry true (no bounds() cull).  d[i] = distance, shape[i] = ordinal
@@ -459,7 +509,11 @@ int pt_set_option(pt_ctx *ctx, const char *key, int value);
  * "mesh_emit_ms"), "guides_valid", "moments", "moments_valid", "moment_frames"
  * (n; 0 while not valid), "variance_ms" (the last variance kernel, of
  * pt_read_variance or pt_denoise_guided), "guided_ms" (all iterations of the
- * last pt_denoise_guided, as "denoise_ms"), "gen_trace" / "gen_norec"
+ * last pt_denoise_guided, as "denoise_ms"), "history_valid", "history_views"
+ * (the accumulates since the history was last dropped), "temporal_ms" (the last
+ * pt_temporal_accumulate's kernel), "history_variance_ms" / "history_denoise_ms"
+ * (the last pt_denoise_history's variance kernel / all its iterations),
+ * "gen_trace" / "gen_norec"
  * (the last timed binned dispatch's first pass made its own camera rays /
  * and stored no ray records for shade pass 0). */
 int pt_get_option(pt_ctx *ctx, const char *key, double *value);
