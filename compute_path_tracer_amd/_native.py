@@ -98,6 +98,7 @@ class TemporalParams(Structure):
 
 
 PT_MESH_BRICK, PT_MESH_MAX_CELLS, PT_MESH_MAX_PROJECT = 8, 1024, 8
+PT_RAYS_MAX = 1 << 26  # rays or pixels per pt_trace_rays / pt_pick_pixels call
 
 
 class MeshDesc(Structure):
@@ -221,6 +222,9 @@ SIGNATURES = {
     "pt_sample_field": (c_int, [_ctx, _f32p, c_uint32, _f32p, POINTER(c_int32)]),
     "pt_mesh_extract": (c_int, [_ctx, POINTER(MeshDesc), POINTER(MeshInfo)]),
     "pt_mesh_read": (c_int, [_ctx, _f32p, _f32p, POINTER(c_int32), _u32p, c_size_t, c_size_t]),
+    "pt_trace_rays": (c_int, [_ctx, _f32p, _f32p, c_uint32, _f32p, POINTER(c_int32), _f32p]),
+    "pt_pick_pixels": (c_int, [_ctx, POINTER(Constants), POINTER(Settings), POINTER(c_int32), c_uint32, _f32p,
+                               POINTER(c_int32), _f32p]),
     "pt_probe_map": (c_int, [_ctx, c_int, c_int, c_uint32, _f32p, _u64p, _f32p, _u64p, c_int, _f32p, POINTER(c_int32),
                              _u64p, _u64p]),
     "pt_probe_taps": (c_int, [_ctx, c_int, c_uint32, _f32p, _u64p, _f32p, _f32p, POINTER(c_int32), _u64p, _u64p]),

@@ -241,6 +241,12 @@ struct pt_ctx {
             return n;
         }
     } mesh;
+    // ray queries (pt_trace_rays / pt_pick_pixels): the staging of a call's rays or pixel list
+    // and of its answers, grown on first use; the timing of each entry point's kernel
+    struct Rays {
+        DevBuf ro, rd, xy, t, shape, normal;
+        TimedSection rays_time, pick_time;
+    } rays;
     // the probes (pt_probe_map / pt_probe_taps / pt_probe_bounds, pt_map_probe.hip): the probe
     // modules loaded so far by their generated source, how many were compiled and in how many seconds, and the
     // staging of a call's inputs and outputs, grown on first use

@@ -24,6 +24,16 @@ void pt_launch_bin_sky(const PtPass &P, bool quads, unsigned grid, hipStream_t s
 void pt_launch_display(const float *img, uint32_t w, uint32_t h, int fmt, void *out, hipStream_t stream);
 // the denoiser's guide images (pt_render_guides): L as a dispatch takes it, over every tile, a lens as its pinhole
 void pt_launch_guides(const PtLaunch &L, float *g0, float *g1, hipStream_t stream);
+// ray queries (pt_trace_rays / pt_pick_pixels): L as pt_launch_guides takes it; device pointers, any
+// output nullptr.  rays: n caller rays, ro and rd [n][3].  pick: xy [n][2] pixels inside the image, answers in list
+// order; or xy nullptr and n = L.n_tiles * 64 threads, one per tile pixel, answers in image order
+#ifndef PT_RAYS_BLOCK              // (an A/B build may set it: build.build_variant)
+#define PT_RAYS_BLOCK 64           // threads per block of both kernels (64 against 256: EXPERIMENTS.md)
+#endif
+void pt_launch_rays(const PtLaunch &L, const float *ro, const float *rd, uint32_t n, float *t, int32_t *shape, float *normal,
+                    hipStream_t stream);
+void pt_launch_pick(const PtLaunch &L, const int32_t *xy, uint32_t n, float *t, int32_t *shape, float *normal,
+                    hipStream_t stream);
 // one iteration of the a-trous filter (pt_denoise): every iteration's constants travel in the launch arguments
 #define PT_ATROUS_BX 64            // direct form: block 64 x 4, a wave = one row segment
 #define PT_ATROUS_BY 4

@@ -170,6 +170,9 @@ const Option kOptions[] = {
     OPT_GET("mesh_scan_ms", section_ms(c, c->mesh.stage_time[pt_ctx::Mesher::kScan], false, v)),
     OPT_GET("mesh_emit_ms", section_ms(c, c->mesh.stage_time[pt_ctx::Mesher::kEmit], false, v)),
     OPT_GET("mesh_ms", mesh_ms(c, v)),
+    // the last pt_trace_rays' / pt_pick_pixels' kernel (both calls waited for it)
+    OPT_GET("rays_ms", section_ms(c, c->rays.rays_time, false, v)),
+    OPT_GET("pick_ms", section_ms(c, c->rays.pick_time, false, v)),
     OPT_READ("guides_valid", c->dn.guides_valid ? 1.0 : 0.0),
     // second moments: whether the moment image and the accumulation image are one render's, and of how many frames;
     // the last variance kernel, and all iterations of the last pt_denoise_guided (without its variance and display passes)

@@ -491,6 +491,99 @@ int pt_read_guides(pt_ctx *c, float *g0, float *g1, size_t bytes_each) {
     return read_back(c, g1, bytes_each, c->dn.guides[1].p, g1 ? need : 0, nullptr);
 }
 
+// ---- ray queries ------------------------------------------------
+// The launch block of a query, built as pt_render_guides builds its own: every tile, a lens as its pinhole, no sky.
+// Nothing of the context changes: the image, the guides and their valid flag, the moments and the history stay.
+static int make_query_launch(pt_ctx *c, const pt_constants *k, const pt_settings *s, PtLaunch &L) {
+    const int rc = make_launch(c, k, s, 1, L);
+    if (rc != PT_OK) return rc;
+    L.n_tiles = int32_t(int64_t(L.tiles_x) * int64_t((c->img.height + PT_TILE - 1) / PT_TILE));
+    L.rank = 0;
+    L.nranks = 1;
+    if (L.cam_mode == PT_CAM_LENS) L.cam_mode = PT_CAM_PINHOLE;
+    L.sky_mode = PT_SKY_OFF;
+    L.write = 0;
+    return PT_OK;
+}
+
+// the answers' staging for n rays (only what is asked for), then, after the kernel, their way back and the wait
+static int query_outputs(pt_ctx *c, uint32_t n, const float *t, const int32_t *shape, const float *normal) {
+    pt_ctx::Rays &r = c->rays;
+    int rc;
+    if (t && (rc = ensure(c, r.t, size_t(n) * 4)) != PT_OK) return rc;
+    if (shape && (rc = ensure(c, r.shape, size_t(n) * 4)) != PT_OK) return rc;
+    if (normal && (rc = ensure(c, r.normal, size_t(n) * 12)) != PT_OK) return rc;
+    return PT_OK;
+}
+
+static int query_read_back(pt_ctx *c, uint32_t n, float *t, int32_t *shape, float *normal) {
+    pt_ctx::Rays &r = c->rays;
+    if (t) HIPCHK(c, hipMemcpyAsync(t, r.t.p, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (shape) HIPCHK(c, hipMemcpyAsync(shape, r.shape.p, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (normal) HIPCHK(c, hipMemcpyAsync(normal, r.normal.p, size_t(n) * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_trace_rays(pt_ctx *c, const float *ro, const float *rd, uint32_t n, float *t, int32_t *shape, float *normal) {
+    if (!c) return PT_ERR_INVALID;
+    if (n > PT_RAYS_MAX) return fail(c, PT_ERR_INVALID, "more than PT_RAYS_MAX rays");
+    if (n && (!ro || !rd)) return fail(c, PT_ERR_INVALID, "null ray origins / directions");
+    // (a query reads no constants and no settings: the launch block wants some)
+    const pt_constants k = {0.0f, 0, 1.0f, 0};
+    const pt_settings s = {0, 0, 1.0f, 1.0f, 0};
+    PtLaunch L;
+    int rc = make_query_launch(c, &k, &s, L);
+    if (rc != PT_OK) return rc;
+    if (!n) return PT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    pt_ctx::Rays &r = c->rays;
+    if ((rc = ensure(c, r.ro, size_t(n) * 12)) != PT_OK) return rc;
+    if ((rc = ensure(c, r.rd, size_t(n) * 12)) != PT_OK) return rc;
+    if ((rc = query_outputs(c, n, t, shape, normal)) != PT_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(r.ro.p, ro, size_t(n) * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.rd.p, rd, size_t(n) * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, r.rays_time.begin(c->stream));
+    pt_launch_rays(L, r.ro.as<float>(), r.rd.as<float>(), n, t ? r.t.as<float>() : nullptr,
+                   shape ? r.shape.as<int32_t>() : nullptr, normal ? r.normal.as<float>() : nullptr, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, r.rays_time.end(c->stream));
+    return query_read_back(c, n, t, shape, normal);
+}
+
+int pt_pick_pixels(pt_ctx *c, const pt_constants *k, const pt_settings *s, const int32_t *xy, uint32_t n, float *t,
+                   int32_t *shape, float *normal) {
+    if (!c) return PT_ERR_INVALID;
+    if (n > PT_RAYS_MAX) return fail(c, PT_ERR_INVALID, "more than PT_RAYS_MAX pixels");
+    PtLaunch L;
+    int rc = make_query_launch(c, k, s, L);
+    if (rc != PT_OK) return rc;
+    if (!n) return PT_OK;
+    const uint32_t w = c->img.width, h = c->img.height;
+    if (!xy) {
+        if (uint64_t(n) != uint64_t(w) * uint64_t(h))
+            return fail(c, PT_ERR_INVALID, "a NULL pixel list means every pixel: n must be width * height");
+    } else {
+        for (uint32_t i = 0; i < n; ++i) {
+            const int32_t x = xy[2 * size_t(i)], y = xy[2 * size_t(i) + 1];
+            if (x < 0 || y < 0 || uint32_t(x) >= w || uint32_t(y) >= h) return fail(c, PT_ERR_INVALID, "pixel outside the image");
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    pt_ctx::Rays &r = c->rays;
+    if (xy && (rc = ensure(c, r.xy, size_t(n) * 8)) != PT_OK) return rc;
+    if ((rc = query_outputs(c, n, t, shape, normal)) != PT_OK) return rc;
+    if (xy) HIPCHK(c, hipMemcpyAsync(r.xy.p, xy, size_t(n) * 8, hipMemcpyHostToDevice, c->stream));
+    // the list: one thread per entry; every pixel: one per pixel of every tile, as the guide kernel
+    const uint32_t threads = xy ? n : uint32_t(L.n_tiles) * 64u;
+    HIPCHK(c, r.pick_time.begin(c->stream));
+    pt_launch_pick(L, xy ? r.xy.as<int32_t>() : nullptr, threads, t ? r.t.as<float>() : nullptr,
+                   shape ? r.shape.as<int32_t>() : nullptr, normal ? r.normal.as<float>() : nullptr, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, r.pick_time.end(c->stream));
+    return query_read_back(c, n, t, shape, normal);
+}
+
 int pt_denoise(pt_ctx *c, const pt_denoise_params *p, int format, void *out, size_t bytes) {
     if (!c) return PT_ERR_INVALID;
     if (!p) return fail(c, PT_ERR_INVALID, "null denoise parameters");

@@ -11,7 +11,7 @@ launch that keeps the accumulation texel in registers.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -19,6 +19,35 @@ from . import _native as N
 from .mesh import Mesh, mesh_grid
 from .sdf_editor import Program
 from .view import look_at_camera, sky_light
+
+
+class RayHits(NamedTuple):
+    """What ``trace_rays`` / ``pick_pixels`` / ``id_image`` return, each array
+    shaped like the query's leading dimensions: ``t`` float32 (the march
+    parameter; a miss keeps CastRay's value, > 100), ``hit`` bool
+    (``~(t > 100)``: a NaN t is a hit, as in the render), ``shape`` int32 (the
+    ordinal of the program's SHAPE op, -1 = none), ``normal`` float32 [..., 3]
+    (zeros where not hit), ``point`` float32 [..., 3] (origin + direction * t,
+    NaN rows where not hit)."""
+
+    t: np.ndarray
+    hit: np.ndarray
+    shape: np.ndarray
+    normal: np.ndarray
+    point: np.ndarray
+
+
+class Pick(NamedTuple):
+    """One pixel's ``pick``: ``hit``, ``t``, ``point`` and ``normal`` (float32
+    [3]), ``shape`` (ordinal, -1 = none) and ``node``, the editor's ``Shape``
+    behind it (None on a miss or without an editor)."""
+
+    hit: bool
+    t: float
+    point: np.ndarray
+    normal: np.ndarray
+    shape: int
+    node: object
 
 
 def default_settings() -> N.Settings:
@@ -470,6 +499,92 @@ class PathTracer:
         self._chk("pt_sample_field", self._L.pt_sample_field(self._ctx, N.fptr(p), len(p), N.fptr(d),
                                                               N.ptr(s, ctypes.c_int32)))
         return d, s
+
+    # -- ray queries (new: what a ray hits) ----------------------------------
+    @staticmethod
+    def _ray_hits(lead, origins, directions, t, shape, normal) -> RayHits:
+        with np.errstate(all="ignore"):
+            hit = ~(t > np.float32(100.0))
+            point = origins + directions * t[:, None]  # (float32: one rounding per step)
+        point[~hit] = np.nan
+        return RayHits(t.reshape(lead), hit.reshape(lead), shape.reshape(lead), normal.reshape(*lead, 3),
+                       point.reshape(*lead, 3))
+
+    def trace_rays(self, origins, directions) -> RayHits:
+        """pt_trace_rays: bounds / CastRay / calc_normal along caller rays
+        (float [..., 3] each, the same shape).  A direction is used as given,
+        not normalised; a ray with a non-finite component is not traced
+        (t = NaN, shape -1, zero normal: a hit by the NaN rule)."""
+        o = np.ascontiguousarray(origins, np.float32)
+        d = np.ascontiguousarray(directions, np.float32)
+        if o.shape != d.shape or o.ndim < 1 or o.shape[-1] != 3:
+            raise ValueError(f"origins and directions must both be (..., 3), got {o.shape} and {d.shape}")
+        lead, o, d = o.shape[:-1], o.reshape(-1, 3), d.reshape(-1, 3)
+        n = len(o)
+        t, shape, normal = np.empty(n, np.float32), np.empty(n, np.int32), np.empty((n, 3), np.float32)
+        self._chk("pt_trace_rays", self._L.pt_trace_rays(self._ctx, N.fptr(o), N.fptr(d), n, N.fptr(t),
+                                                          N.ptr(shape, ctypes.c_int32), N.fptr(normal)))
+        return self._ray_hits(lead, o, d, t, shape, normal)
+
+    def _pixel_rays(self, xy, constants):
+        """(origins, directions) float32 [n][3] of pixels' jitter-free primary
+        rays, in the steps the guide kernel takes (a lens as its pinhole)."""
+        F = np.float32
+        w, h = self.size
+        cam, dflt = self.get_camera()
+        with np.errstate(all="ignore"):
+            ux = ((xy[:, 0].astype(F) / F(w)) * F(2.0) - F(1.0)) * F(constants.aspect)
+            uy = (xy[:, 1].astype(F) / F(h)) * F(2.0) - F(1.0)
+            fov = F(self.settings.fov)
+            if dflt:
+                v = np.stack([ux, uy, np.full(len(xy), fov, F)], -1)
+                o = np.tile(np.array([0.0, 0.0, -3.0], F), (len(xy), 1))
+            else:
+                r, u, f = (np.array(list(a), F) for a in (cam.right, cam.up, cam.forward))
+                v = (r * ux[:, None] + u * uy[:, None]) + f * fov
+                o = np.tile(np.array(list(cam.origin), F), (len(xy), 1))
+            l = np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+            return o, (v / l[:, None]).astype(F)
+
+    def pick_pixels(self, xy=None, constants: Optional[N.Constants] = None) -> RayHits:
+        """pt_pick_pixels: the first hit under pixels ``xy`` (int [..., 2] of
+        (x, y); None: every pixel, shaped (height, width)) along the rays
+        ``render_guides`` casts -- jitter-free, the camera in force with a lens
+        as its pinhole, aspect as ``render_guides`` forms it (or explicit
+        ``constants``) -- so ``normal`` and ``t`` are the guide plane g0 bit
+        for bit.  Nothing of the context changes."""
+        c = self._constants(0) if constants is None else constants
+        w, h = self.size
+        if xy is None:
+            lead = (h, w)
+            ys, xs = np.divmod(np.arange(w * h, dtype=np.int32), np.int32(max(w, 1)))
+            p, pp = np.stack([xs, ys], -1).astype(np.int32), None
+        else:
+            p = np.ascontiguousarray(xy, np.int32)
+            if p.ndim < 1 or p.shape[-1] != 2:
+                raise ValueError(f"xy must be (..., 2), got {p.shape}")
+            lead, p = p.shape[:-1], p.reshape(-1, 2)
+            pp = N.ptr(p, ctypes.c_int32)
+        n = len(p)
+        t, shape, normal = np.empty(n, np.float32), np.empty(n, np.int32), np.empty((n, 3), np.float32)
+        self._chk("pt_pick_pixels", self._L.pt_pick_pixels(self._ctx, ctypes.byref(c), ctypes.byref(self.settings), pp, n,
+                                                            N.fptr(t), N.ptr(shape, ctypes.c_int32), N.fptr(normal)))
+        o, d = self._pixel_rays(p, c)
+        return self._ray_hits(lead, o, d, t, shape, normal)
+
+    def id_image(self, constants: Optional[N.Constants] = None) -> RayHits:
+        """The shape-id image: ``pick_pixels`` of every pixel, arrays shaped
+        (height, width), rows as read_image."""
+        return self.pick_pixels(None, constants)
+
+    def pick(self, x: int, y: int, editor=None) -> Pick:
+        """What is under pixel (x, y): a click in an editor.  ``editor`` (the
+        SDFEditor the program was compiled from) maps the shape ordinal to its
+        ``Shape`` node (``editor.shape_nodes()``)."""
+        r = self.pick_pixels([(int(x), int(y))])
+        shape, hit = int(r.shape[0]), bool(r.hit[0])
+        node = editor.shape_nodes()[shape] if editor is not None and hit and shape >= 0 else None
+        return Pick(hit, float(r.t[0]), r.point[0], r.normal[0], shape, node)
 
     # -- point probes (tests: the scene's map() and bounds() per input) ---------
     PROBE_KINDS = {"interp": N.PT_PROBE_INTERP, "table": N.PT_PROBE_TABLE, "baked": N.PT_PROBE_BAKED}

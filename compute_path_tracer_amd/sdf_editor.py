@@ -529,3 +529,12 @@ class SDFEditor:
 
     def rows(self) -> List[dict]:
         return flatten(self.header_unions)[0]
+
+    def shape_nodes(self) -> List[Shape]:
+        """The tree's shapes in the order of the compiled program's
+        PT_OP_SHAPE ops: element k is the node behind shape ordinal k (what
+        ``PathTracer.pick`` / ``trace_rays`` / ``sample_field`` and a mesh's
+        ``shapes`` report).  The compiler emits a union's child unions, then
+        its shapes -- ``flatten``'s order, which ``compile`` pairs with the
+        shape ops one for one."""
+        return [o for o in flatten(self.header_unions)[1] if isinstance(o, Shape)]

@@ -461,6 +461,38 @@ int pt_mesh_extract(pt_ctx *ctx, const pt_mesh_desc *g, pt_mesh_info *info);
  * a cap is too small for an array that is asked for. */
 int pt_mesh_read(pt_ctx *ctx, float *positions, float *normals, int32_t *shapes, uint32_t *triangles,
                  size_t vertex_cap, size_t triangle_cap);
+/* Ray queries (new): what a ray hits.  For one ray (ro, rd):
+ *   a non-finite component among the six: t = NaN, shape = -1, n = (0, 0, 0)
+ *     (answered by definition, not traced);
+ *   check = bounds(ro, rd); (t, m) = CastRay(ro, rd, check)   (STEPS, MHD, FP
+ *     of the reference); hit = !(t > FP) (a NaN t is a hit, as in the render);
+ *   hit:  n = calc_normal(ro + rd * t, check) (what pt_render_guides stores in
+ *         g0.xyz), shape = ordinal of the PT_OP_SHAPE op (as pt_sample_field's,
+ *         -1 = MDEF);
+ *   miss: n = (0, 0, 0), shape = -1, t as CastRay returned it.
+ * rd is used as given, not normalised: t is the march parameter, so a
+ * direction longer than 1 oversteps the surface and a shorter one creeps; a
+ * zero direction marches in place until t > FP or 80 steps.  No random
+ * numbers; pt_set_tiles, the debug view, the sky, the accumulation image, the
+ * guides and their valid flag neither enter nor change: only the outputs are
+ * written.
+ * pt_trace_rays: n caller rays, ro and rd 3 floats each; t and shape one
+ * value per ray, normal 3 floats per ray.  Any output may be NULL.  Blocking,
+ * on the context's stream.  n = 0 is a no-op.  PT_ERR_INVALID for a NULL
+ * context, NULL ro or rd (n > 0) or n > PT_RAYS_MAX (refused before anything
+ * is read); PT_ERR_STATE without program or data.
+ * pt_pick_pixels: the same for the jitter-free primary rays of n pixels, xy 2
+ * ints each (x, y), under the camera in force with a lens taken as its
+ * pinhole, aspect from c and fov from s: the rays of pt_render_guides, so
+ * (normal, t) of a pixel equal its g0 bit for bit and its shape's albedo is
+ * g1.rgb.  xy = NULL means every pixel in image order (row y, then x) and n
+ * must be width * height: the shape-id image.  PT_ERR_INVALID also for NULL c
+ * or s, for a NULL list with another n and for a listed pixel outside the
+ * image (checked before any launch: nothing is written). */
+#define PT_RAYS_MAX 67108864 /* 1u << 26 rays or pixels per call */
+int pt_trace_rays(pt_ctx *ctx, const float *ro, const float *rd, uint32_t n, float *t, int32_t *shape, float *normal);
+int pt_pick_pixels(pt_ctx *ctx, const pt_constants *c, const pt_settings *s, const int32_t *xy, uint32_t n, float *t,
+                   int32_t *shape, float *normal);
 /* Tuning knobs: "kernel" (0 auto = 3, 1 simple one-path-per-lane, 2 tile-
  * resident wavefront state machine, 3 mask-binned passes: per bounce, the
  * rays of a chunk of frames are grouped by their bounds() check set before
@@ -506,7 +538,8 @@ int pt_set_option(pt_ctx *ctx, const char *key, int value);
  * last pt_denoise, without its display pass), "mesh_skip", "sample_ms" (the
  * last pt_sample_field's kernel), "mesh_ms" (the last pt_mesh_extract's
  * kernels, the sum of "mesh_skip_ms", "mesh_classify_ms", "mesh_scan_ms" and
- * "mesh_emit_ms"), "guides_valid", "moments", "moments_valid", "moment_frames"
+ * "mesh_emit_ms"), "rays_ms" / "pick_ms" (the last pt_trace_rays' /
+ * pt_pick_pixels' kernel), "guides_valid", "moments", "moments_valid", "moment_frames"
  * (n; 0 while not valid), "variance_ms" (the last variance kernel, of
  * pt_read_variance or pt_denoise_guided), "guided_ms" (all iterations of the
  * last pt_denoise_guided, as "denoise_ms"), "history_valid", "history_views"
