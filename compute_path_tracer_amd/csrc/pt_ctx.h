@@ -1,5 +1,6 @@
 // pt_ctx.h -- the context behind the C ABI (include/pt_abi.h) and the small
-// helpers its host files share: pt_runtime.hip (the entry points),
+// helpers its host files share: pt_runtime.hip (the entry points of the
+// context and the scene), pt_post_host.cpp (the image-space entry points),
 // pt_bin_host.cpp (the binned scheduler) and pt_options.cpp (the option table).
 // Host only: no device header and no hipRTC source includes it.
 #pragma once

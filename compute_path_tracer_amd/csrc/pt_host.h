@@ -1,5 +1,5 @@
-// pt_host.h -- host-side internals shared by the runtime's host files (pt_runtime.hip, pt_bin_host.cpp,
-// pt_options.cpp, pt_derive.cpp), the scene-kernel generator (pt_jit.cpp), the scene kernels' hipRTC build and
+// pt_host.h -- host-side internals shared by the runtime's host files (pt_runtime.hip, pt_post_host.cpp,
+// pt_bin_host.cpp, pt_options.cpp, pt_derive.cpp), the scene-kernel generator (pt_jit.cpp), the scene kernels' hipRTC build and
 // on-disk cache (pt_jit_build.cpp) and their loading and lifecycle (pt_jit_state.cpp).
 #pragma once
 
@@ -12,7 +12,7 @@
 #include "pt_binned.h"
 #include "pt_device.h"
 
-// ahead-of-time kernels (pt_kernel.hip)
+// ahead-of-time scene kernels (pt_kernel.hip; the image-space kernels' launches are in pt_post.h)
 bool pt_use_simple_kernel(const PtLaunch &L);
 void pt_launch_render(const PtLaunch &L, bool stats, hipStream_t stream);
 enum class PtBinStage { Gen, Shade, Scan, Scatter, Trace, Fold };
@@ -21,7 +21,6 @@ int pt_bin_trace_blocks_per_cu(bool stats);  // occupancy of the interpreter tra
 // the sky pass after a binned trace pass (pt_set_sky): P as that trace pass's shade pass takes it; quads: the
 // trace pass wrote hit quads (taps in the shade pass), not hit records
 void pt_launch_bin_sky(const PtPass &P, bool quads, unsigned grid, hipStream_t stream);
-void pt_launch_display(const float *img, uint32_t w, uint32_t h, int fmt, void *out, hipStream_t stream);
 // the denoiser's guide images (pt_render_guides): L as a dispatch takes it, over every tile, a lens as its pinhole
 void pt_launch_guides(const PtLaunch &L, float *g0, float *g1, hipStream_t stream);
 // ray queries (pt_trace_rays / pt_pick_pixels): L as pt_launch_guides takes it; device pointers, any
@@ -34,65 +33,11 @@ void pt_launch_rays(const PtLaunch &L, const float *ro, const float *rd, uint32_
                     hipStream_t stream);
 void pt_launch_pick(const PtLaunch &L, const int32_t *xy, uint32_t n, float *t, int32_t *shape, float *normal,
                     hipStream_t stream);
-// one iteration of the a-trous filter (pt_denoise): every iteration's constants travel in the launch arguments
-#define PT_ATROUS_BX 64            // direct form: block 64 x 4, a wave = one row segment
-#define PT_ATROUS_BY 4
-#define PT_ATROUS_T 16             // LDS form: 16 x 16 tile + halo
-#define PT_ATROUS_LDS_MAX_STEP 2   // ... for steps 1 and 2
-struct PtAtrous {
-    const float4 *in, *g0, *g1;
-    float4 *out;
-    int32_t w, h;
-    int32_t iter;   // taps at step 1 << iter
-    int32_t npow;   // normal_power_log2
-    float ka;
-    float kc[PT_DENOISE_MAX_ITERATIONS], kz[PT_DENOISE_MAX_ITERATIONS];
-};
-void pt_launch_atrous(const PtAtrous &A, bool lds, hipStream_t stream);
 // second moments (pt_set_option "moments"): the simple kernel and the binned fold that also mix
 // each frame's squared colour into the moment image (debug 0, write 1 only; launched instead of pt_render_kernel /
 // pt_bin_fold_kernel while the option is on)
 void pt_launch_render_m(const PtLaunch &L, float *moments, hipStream_t stream);
 void pt_launch_bin_fold_m(const PtPass &P, float *moments, unsigned grid, hipStream_t stream);
-// v[i] = ((vr + vg) + vb), v.k = max(M.k - A.k * A.k, 0) / nm1, over n texels (pt_read_variance)
-void pt_launch_variance(const float *accum, const float *moments, float *v, uint32_t n, float nm1, hipStream_t stream);
-// one iteration of the variance-guided filter (pt_denoise_guided): PtAtrous's taps with a per-pixel colour
-// constant from the 3x3-smoothed variance plane, which is filtered beside the colour (vin -> vout)
-struct PtGuided {
-    const float4 *in, *g0, *g1;
-    const float *vin;
-    float4 *out;
-    float *vout;
-    int32_t w, h;
-    int32_t iter;   // taps at step 1 << iter
-    int32_t npow;   // normal_power_log2
-    float ka;
-    float sv2;      // sigma_variance squared
-    float kz[PT_DENOISE_MAX_ITERATIONS];
-};
-void pt_launch_guided(const PtGuided &A, bool lds, hipStream_t stream);  // lds: staged taps at steps 1 and 2
-// temporal accumulation (pt_temporal_accumulate): the current view -- image, moments, guides, of
-// n_cur frames, under (cam_mode, cam, aspect, fov) -- merged with the history of the previous view (p*: its colour,
-// moments, count and guide planes, its camera, and that camera's origin and reciprocal basis) into the new history
-// (o*).  have 0: nothing is taken and no p* pointer is read (no history yet, or a degenerate previous basis)
-struct PtTemporal {
-    const float4 *a, *m, *g0, *g1;
-    const float4 *ph, *phm, *pg0, *pg1;
-    const float *phn;
-    float4 *oh, *ohm;
-    float *ohn;
-    int32_t w, h;
-    int32_t have;
-    int32_t cam_mode, pcam_mode;  // PT_CAM_DEFAULT or PT_CAM_PINHOLE (a lens as its pinhole)
-    float n_cur;
-    float aspect, fov, paspect, pfov;
-    float max_history, depth_tolerance, normal_cos, at2;  // at2 = albedo_tolerance squared
-    float po[3], ir[3], iu[3], ifw[3];
-    pt_camera cam, pcam;
-};
-void pt_launch_temporal(const PtTemporal &T, hipStream_t stream);
-// v[i] as pt_launch_variance with a count per texel: v.k = max(HM.k - H.k * H.k, 0) / (HN - 1) (pt_denoise_history)
-void pt_launch_history_variance(const float *h, const float *hm, const float *hn, float *v, uint32_t n, hipStream_t stream);
 
 // Expand (program, data[]) into the device tables (see pt_device.h).
 int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, const float *data, uint32_t n,

@@ -1,4 +1,6 @@
-// pt_runtime.hip -- implementation of the C ABI in include/pt_abi.h.
+// pt_runtime.hip -- implementation of the C ABI in include/pt_abi.h: the context, the scene, the dispatch and the
+// scene-side queries.  (The image-space entry points -- display, variance, the filters, temporal accumulation --
+// are in pt_post_host.cpp, the mesh export in pt_mesh_host.cpp.)
 //
 // Owns what the reference's wgpu objects owned (path_tracer.rs:18-163,
 // structs.rs:113-184, primitives.rs:59-157): the RGBA32F accumulation image,
@@ -26,9 +28,6 @@ static_assert(sizeof(pt_scene_node) == 33 * 4, "pt_scene_node layout");
 static_assert(PT_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "RCCL unique id size");
 static_assert(sizeof(pt_camera) == 14 * 4, "pt_camera layout");
 static_assert(sizeof(pt_sky) == 13 * 4, "pt_sky layout");
-static_assert(sizeof(pt_denoise_params) == 5 * 4, "pt_denoise_params layout");
-static_assert(sizeof(pt_guided_params) == 5 * 4, "pt_guided_params layout");
-static_assert(sizeof(pt_temporal_params) == 4 * 4, "pt_temporal_params layout");
 
 static int alloc_image(pt_ctx *c, uint32_t w, uint32_t h) {
     c->img.accum.release();
@@ -411,59 +410,26 @@ int pt_write_moments(pt_ctx *c, const float *rgba, size_t bytes, uint32_t frames
     return PT_OK;
 }
 
-// the variance plane of the two images into mom.var[0] (asynchronous, timed)
-static int launch_variance(pt_ctx *c) {
-    const size_t texels = size_t(c->img.width) * c->img.height;
-    int rc;
-    for (DevBuf &v : c->mom.var)
-        if ((rc = ensure(c, v, std::max<size_t>(texels * sizeof(float), 16))) != PT_OK) return rc;
-    HIPCHK(c, c->mom.variance_time.begin(c->stream));
-    pt_launch_variance(c->img.accum.as<float>(), c->mom.img.as<float>(), c->mom.var[0].as<float>(), uint32_t(texels),
-                       float(c->mom.frames - 1u), c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, c->mom.variance_time.end(c->stream));
-    return PT_OK;
-}
-
-static const char *const kNoVariance = "no variance: valid moments of at least 2 frames are needed";
-
-int pt_read_variance(pt_ctx *c, float *v, size_t bytes) {
-    if (!c) return PT_ERR_INVALID;
-    if (!c->mom.valid || c->mom.frames < 2) return fail(c, PT_ERR_STATE, kNoVariance);
-    const size_t need = c->img.bytes(sizeof(float));
-    if (!v || bytes < need) return fail(c, PT_ERR_SIZE, "variance buffer too small");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int rc = launch_variance(c);
+// The launch block of one jitter-free primary ray per pixel (the guide images, the ray queries): every tile, whatever
+// pt_set_tiles says; a lens as its pinhole (no lens draw, no rng at all); no sky; the image is not written (none of
+// these kernels reads the flag: they store to their own planes).  Nothing of the context changes.
+static int make_query_launch(pt_ctx *c, const pt_constants *k, const pt_settings *s, PtLaunch &L) {
+    const int rc = make_launch(c, k, s, 1, L);
     if (rc != PT_OK) return rc;
-    return read_back(c, v, bytes, c->mom.var[0].p, need, nullptr);
-}
-
-int pt_display(pt_ctx *c, int format, void *out, size_t bytes) {
-    if (!c) return PT_ERR_INVALID;
-    if (format != PT_DISPLAY_RGBA32F && format != PT_DISPLAY_SRGB8) return fail(c, PT_ERR_INVALID, "bad display format");
-    const size_t need = c->img.bytes(format == PT_DISPLAY_RGBA32F ? 16 : 4);
-    if (!out || bytes < need) return fail(c, PT_ERR_SIZE, "display buffer too small");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure(c, c->img.display, std::max<size_t>(need, 16));
-    if (rc != PT_OK) return rc;
-    HIPCHK(c, c->img.display_time.begin(c->stream));
-    pt_launch_display(c->img.accum.as<float>(), c->img.width, c->img.height, format, c->img.display.p, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, c->img.display_time.end(c->stream));
-    return read_back(c, out, bytes, c->img.display.p, need, nullptr);
-}
-
-// ---- denoiser -------------------------------------------------
-int pt_render_guides(pt_ctx *c, const pt_constants *k, const pt_settings *s) {
-    PtLaunch L;
-    int rc = make_launch(c, k, s, 1, L);
-    if (rc != PT_OK) return rc;
-    // every tile, whatever pt_set_tiles says; a lens as its pinhole (no lens draw, no rng at all)
     L.n_tiles = int32_t(int64_t(L.tiles_x) * int64_t((c->img.height + PT_TILE - 1) / PT_TILE));
     L.rank = 0;
     L.nranks = 1;
     if (L.cam_mode == PT_CAM_LENS) L.cam_mode = PT_CAM_PINHOLE;
     L.sky_mode = PT_SKY_OFF;
+    L.write = 0;
+    return PT_OK;
+}
+
+// ---- denoiser: the guide images (the filters are in pt_post_host.cpp) --------
+int pt_render_guides(pt_ctx *c, const pt_constants *k, const pt_settings *s) {
+    PtLaunch L;
+    int rc = make_query_launch(c, k, s, L);
+    if (rc != PT_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t plane = std::max<size_t>(c->img.bytes(), 16);
     for (DevBuf &g : c->dn.guides)
@@ -492,20 +458,6 @@ int pt_read_guides(pt_ctx *c, float *g0, float *g1, size_t bytes_each) {
 }
 
 // ---- ray queries ------------------------------------------------
-// The launch block of a query, built as pt_render_guides builds its own: every tile, a lens as its pinhole, no sky.
-// Nothing of the context changes: the image, the guides and their valid flag, the moments and the history stay.
-static int make_query_launch(pt_ctx *c, const pt_constants *k, const pt_settings *s, PtLaunch &L) {
-    const int rc = make_launch(c, k, s, 1, L);
-    if (rc != PT_OK) return rc;
-    L.n_tiles = int32_t(int64_t(L.tiles_x) * int64_t((c->img.height + PT_TILE - 1) / PT_TILE));
-    L.rank = 0;
-    L.nranks = 1;
-    if (L.cam_mode == PT_CAM_LENS) L.cam_mode = PT_CAM_PINHOLE;
-    L.sky_mode = PT_SKY_OFF;
-    L.write = 0;
-    return PT_OK;
-}
-
 // the answers' staging for n rays (only what is asked for), then, after the kernel, their way back and the wait
 static int query_outputs(pt_ctx *c, uint32_t n, const float *t, const int32_t *shape, const float *normal) {
     pt_ctx::Rays &r = c->rays;
@@ -582,332 +534,6 @@ int pt_pick_pixels(pt_ctx *c, const pt_constants *k, const pt_settings *s, const
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, r.pick_time.end(c->stream));
     return query_read_back(c, n, t, shape, normal);
-}
-
-int pt_denoise(pt_ctx *c, const pt_denoise_params *p, int format, void *out, size_t bytes) {
-    if (!c) return PT_ERR_INVALID;
-    if (!p) return fail(c, PT_ERR_INVALID, "null denoise parameters");
-    if (format != PT_DISPLAY_RGBA32F && format != PT_DISPLAY_SRGB8 && format != PT_DENOISE_LINEAR)
-        return fail(c, PT_ERR_INVALID, "bad denoise format");
-    if (p->iterations < 1 || p->iterations > PT_DENOISE_MAX_ITERATIONS)
-        return fail(c, PT_ERR_INVALID, "denoise iterations must be in [1, 8]");
-    if (p->normal_power_log2 > 8) return fail(c, PT_ERR_INVALID, "denoise normal_power_log2 must be in [0, 8]");
-    for (float v : {p->sigma_color, p->sigma_depth, p->sigma_albedo})
-        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "denoise sigma must be finite and >= 0");
-    // the iterations' constants, in f32: the scaled sigma, its square, one
-    // division of 1 (a term that is off: 0)
-    PtAtrous A;
-    std::memset(&A, 0, sizeof A);
-    auto inv_sq = [](float sigma, float scale) {
-        if (sigma == 0.0f) return 0.0f;
-        const float v = sigma * scale;
-        const float sq = v * v;
-        return 1.0f / sq;
-    };
-    A.ka = inv_sq(p->sigma_albedo, 1.0f);
-    bool finite = std::isfinite(A.ka);
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        A.kc[i] = inv_sq(p->sigma_color, std::ldexp(1.0f, -int(i)));
-        A.kz[i] = inv_sq(p->sigma_depth, std::ldexp(1.0f, int(i)));
-        finite = finite && std::isfinite(A.kc[i]) && std::isfinite(A.kz[i]);
-    }
-    if (!finite) return fail(c, PT_ERR_INVALID, "denoise sigma too small: 1 / sigma^2 is not finite");
-    if (!c->dn.guides_valid) return fail(c, PT_ERR_STATE, "guides stale: call pt_render_guides");
-    const size_t texels = size_t(c->img.width) * c->img.height;
-    const size_t need = texels * (format == PT_DISPLAY_SRGB8 ? 4 : 16);
-    if (!out || bytes < need) return fail(c, PT_ERR_SIZE, "denoise output buffer too small");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    for (DevBuf &f : c->dn.filter)
-        if ((rc = ensure(c, f, std::max<size_t>(texels * 16, 16))) != PT_OK) return rc;
-    if (format != PT_DENOISE_LINEAR && (rc = ensure(c, c->img.display, std::max<size_t>(need, 16))) != PT_OK) return rc;
-    A.g0 = c->dn.guides[0].as<const float4>();
-    A.g1 = c->dn.guides[1].as<const float4>();
-    A.w = int32_t(c->img.width);
-    A.h = int32_t(c->img.height);
-    A.npow = int32_t(p->normal_power_log2);
-    // accumulation image -> filter[0] -> filter[1] -> filter[0] ...: the image itself is only read
-    const float *src = c->img.accum.as<float>();
-    HIPCHK(c, c->dn.denoise_time.begin(c->stream));
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        A.in = reinterpret_cast<const float4 *>(src);
-        A.out = c->dn.filter[i & 1].as<float4>();
-        A.iter = int32_t(i);
-        pt_launch_atrous(A, c->dn.lds != 0, c->stream);
-        HIPCHK(c, hipGetLastError());
-        src = c->dn.filter[i & 1].as<float>();
-    }
-    HIPCHK(c, c->dn.denoise_time.end(c->stream));
-    const void *result = src;
-    if (format != PT_DENOISE_LINEAR) {
-        pt_launch_display(src, c->img.width, c->img.height, format, c->img.display.p, c->stream);
-        HIPCHK(c, hipGetLastError());
-        result = c->img.display.p;
-    }
-    return read_back(c, out, bytes, result, need, nullptr);
-}
-
-// The variance-guided form of pt_denoise: its formats, sizes and refusals, the colour
-// constant per pixel from the variance plane, which the iterations filter beside the colour.
-int pt_denoise_guided(pt_ctx *c, const pt_guided_params *p, int format, void *out, size_t bytes) {
-    if (!c) return PT_ERR_INVALID;
-    if (!p) return fail(c, PT_ERR_INVALID, "null denoise parameters");
-    if (format != PT_DISPLAY_RGBA32F && format != PT_DISPLAY_SRGB8 && format != PT_DENOISE_LINEAR)
-        return fail(c, PT_ERR_INVALID, "bad denoise format");
-    if (p->iterations < 1 || p->iterations > PT_DENOISE_MAX_ITERATIONS)
-        return fail(c, PT_ERR_INVALID, "denoise iterations must be in [1, 8]");
-    if (p->normal_power_log2 > 8) return fail(c, PT_ERR_INVALID, "denoise normal_power_log2 must be in [0, 8]");
-    for (float v : {p->sigma_depth, p->sigma_albedo})
-        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "denoise sigma must be finite and >= 0");
-    if (!std::isfinite(p->sigma_variance) || !(p->sigma_variance > 0.0f))
-        return fail(c, PT_ERR_INVALID, "denoise sigma_variance must be finite and > 0");
-    PtGuided A;
-    std::memset(&A, 0, sizeof A);
-    auto inv_sq = [](float sigma, float scale) {  // (as pt_denoise)
-        if (sigma == 0.0f) return 0.0f;
-        const float v = sigma * scale;
-        const float sq = v * v;
-        return 1.0f / sq;
-    };
-    A.ka = inv_sq(p->sigma_albedo, 1.0f);
-    bool finite = std::isfinite(A.ka);
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        A.kz[i] = inv_sq(p->sigma_depth, std::ldexp(1.0f, int(i)));
-        finite = finite && std::isfinite(A.kz[i]);
-    }
-    if (!finite) return fail(c, PT_ERR_INVALID, "denoise sigma too small: 1 / sigma^2 is not finite");
-    A.sv2 = p->sigma_variance * p->sigma_variance;
-    if (!c->dn.guides_valid) return fail(c, PT_ERR_STATE, "guides stale: call pt_render_guides");
-    if (!c->mom.valid || c->mom.frames < 2) return fail(c, PT_ERR_STATE, kNoVariance);
-    const size_t texels = size_t(c->img.width) * c->img.height;
-    const size_t need = texels * (format == PT_DISPLAY_SRGB8 ? 4 : 16);
-    if (!out || bytes < need) return fail(c, PT_ERR_SIZE, "denoise output buffer too small");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    for (DevBuf &f : c->dn.filter)
-        if ((rc = ensure(c, f, std::max<size_t>(texels * 16, 16))) != PT_OK) return rc;
-    if (format != PT_DENOISE_LINEAR && (rc = ensure(c, c->img.display, std::max<size_t>(need, 16))) != PT_OK) return rc;
-    if ((rc = launch_variance(c)) != PT_OK) return rc;  // -> var[0]
-    A.g0 = c->dn.guides[0].as<const float4>();
-    A.g1 = c->dn.guides[1].as<const float4>();
-    A.w = int32_t(c->img.width);
-    A.h = int32_t(c->img.height);
-    A.npow = int32_t(p->normal_power_log2);
-    // accumulation image -> filter[0] -> filter[1] ..., variance var[0] -> var[1] -> var[0] ...: both images only read
-    const float *src = c->img.accum.as<float>();
-    HIPCHK(c, c->mom.guided_time.begin(c->stream));
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        A.in = reinterpret_cast<const float4 *>(src);
-        A.out = c->dn.filter[i & 1].as<float4>();
-        A.vin = c->mom.var[i & 1].as<const float>();
-        A.vout = c->mom.var[(i + 1) & 1].as<float>();
-        A.iter = int32_t(i);
-        pt_launch_guided(A, c->dn.lds != 0, c->stream);
-        HIPCHK(c, hipGetLastError());
-        src = c->dn.filter[i & 1].as<float>();
-    }
-    HIPCHK(c, c->mom.guided_time.end(c->stream));
-    const void *result = src;
-    if (format != PT_DENOISE_LINEAR) {
-        pt_launch_display(src, c->img.width, c->img.height, format, c->img.display.p, c->stream);
-        HIPCHK(c, hipGetLastError());
-        result = c->img.display.p;
-    }
-    return read_back(c, out, bytes, result, need, nullptr);
-}
-
-// ---- temporal accumulation ---------------------------------------
-// The reciprocal basis of (right, up, forward): cross products over the determinant, in double, each component
-// rounded once to f32.  false: the determinant is zero or not finite (nothing can be projected).
-static bool reciprocal_basis(const pt_camera &cam, float ir[3], float iu[3], float ifw[3]) {
-    const double r[3] = {cam.right[0], cam.right[1], cam.right[2]}, u[3] = {cam.up[0], cam.up[1], cam.up[2]},
-                 f[3] = {cam.forward[0], cam.forward[1], cam.forward[2]};
-    auto cross = [](const double a[3], const double b[3], double o[3]) {
-        o[0] = a[1] * b[2] - a[2] * b[1];
-        o[1] = a[2] * b[0] - a[0] * b[2];
-        o[2] = a[0] * b[1] - a[1] * b[0];
-    };
-    double uf[3], fr[3], ru[3];
-    cross(u, f, uf);
-    cross(f, r, fr);
-    cross(r, u, ru);
-    const double det = (r[0] * uf[0] + r[1] * uf[1]) + r[2] * uf[2];
-    if (!std::isfinite(det) || det == 0.0) return false;
-    for (int k = 0; k < 3; ++k) {
-        ir[k] = float(uf[k] / det);
-        iu[k] = float(fr[k] / det);
-        ifw[k] = float(ru[k] / det);
-    }
-    return true;
-}
-
-static const char *const kNoHistory = "no history: call pt_temporal_accumulate";
-
-int pt_temporal_accumulate(pt_ctx *c, const pt_temporal_params *p) {
-    if (!c) return PT_ERR_INVALID;
-    if (!p) return fail(c, PT_ERR_INVALID, "null temporal parameters");
-    for (float v : {p->max_history, p->depth_tolerance, p->albedo_tolerance})
-        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "temporal max_history and tolerances must be finite and >= 0");
-    if (!(p->normal_cos >= -1.0f && p->normal_cos <= 1.0f)) return fail(c, PT_ERR_INVALID, "temporal normal_cos must lie in [-1, 1]");
-    if (c->view.nranks != 1)
-        return fail(c, PT_ERR_UNSUPPORTED, "the history is of the whole image: pt_set_tiles(0, 1), then write the reduced image and moments");
-    if (!c->dn.guides_valid) return fail(c, PT_ERR_STATE, "guides stale: call pt_render_guides");
-    if (!c->mom.valid || c->mom.frames < 2) return fail(c, PT_ERR_STATE, kNoVariance);
-    HIPCHK(c, hipSetDevice(c->device));
-    pt_ctx::History &hs = c->hist;
-    const size_t texels = size_t(c->img.width) * c->img.height;
-    const size_t rgba = std::max<size_t>(texels * 16, 16), plane = std::max<size_t>(texels * sizeof(float), 16);
-    int rc;
-    for (pt_ctx::History::Set &s : hs.set) {
-        for (DevBuf *b : {&s.h, &s.hm, &s.g0, &s.g1})
-            if ((rc = ensure(c, *b, rgba)) != PT_OK) return rc;
-        if ((rc = ensure(c, s.hn, plane)) != PT_OK) return rc;
-    }
-    const pt_ctx::History::Set &prev = hs.set[hs.cur], &next = hs.set[hs.cur ^ 1];
-    PtTemporal T;
-    std::memset(&T, 0, sizeof T);
-    T.a = c->img.accum.as<const float4>();
-    T.m = c->mom.img.as<const float4>();
-    T.g0 = c->dn.guides[0].as<const float4>();
-    T.g1 = c->dn.guides[1].as<const float4>();
-    T.ph = prev.h.as<const float4>();
-    T.phm = prev.hm.as<const float4>();
-    T.phn = prev.hn.as<const float>();
-    T.pg0 = prev.g0.as<const float4>();
-    T.pg1 = prev.g1.as<const float4>();
-    T.oh = next.h.as<float4>();
-    T.ohm = next.hm.as<float4>();
-    T.ohn = next.hn.as<float>();
-    T.w = int32_t(c->img.width);
-    T.h = int32_t(c->img.height);
-    T.n_cur = float(c->mom.frames);
-    T.cam_mode = c->dn.guide_cam_mode;
-    T.cam = c->dn.guide_cam;
-    T.aspect = c->dn.guide_aspect;
-    T.fov = c->dn.guide_fov;
-    T.pcam_mode = hs.cam_mode;
-    T.pcam = hs.cam;
-    T.paspect = hs.aspect;
-    T.pfov = hs.fov;
-    T.max_history = p->max_history;
-    T.depth_tolerance = p->depth_tolerance;
-    T.normal_cos = p->normal_cos;
-    T.at2 = p->albedo_tolerance * p->albedo_tolerance;
-    for (int k = 0; k < 3; ++k) T.po[k] = hs.cam.origin[k];
-    // (a degenerate previous basis: nothing is taken, the history starts again from the current view)
-    T.have = hs.valid && reciprocal_basis(hs.cam, T.ir, T.iu, T.ifw) ? 1 : 0;
-    HIPCHK(c, hs.accumulate_time.begin(c->stream));
-    pt_launch_temporal(T, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hs.accumulate_time.end(c->stream));
-    // the new history's guides are the current view's
-    if (texels) {
-        HIPCHK(c, hipMemcpyAsync(next.g0.p, c->dn.guides[0].p, texels * 16, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(next.g1.p, c->dn.guides[1].p, texels * 16, hipMemcpyDeviceToDevice, c->stream));
-    }
-    hs.cur ^= 1;
-    hs.cam_mode = T.cam_mode;
-    hs.cam = T.cam;
-    hs.aspect = T.aspect;
-    hs.fov = T.fov;
-    hs.valid = true;
-    hs.views += 1;
-    return PT_OK;
-}
-
-int pt_temporal_reset(pt_ctx *c) {
-    if (!c) return PT_ERR_INVALID;
-    c->hist.drop();
-    return PT_OK;
-}
-
-int pt_read_history(pt_ctx *c, float *colour, float *moments, float *count, size_t bytes_rgba) {
-    if (!c) return PT_ERR_INVALID;
-    if (!c->hist.valid) return fail(c, PT_ERR_STATE, kNoHistory);
-    const size_t need = c->img.bytes();
-    if (bytes_rgba < need) return fail(c, PT_ERR_SIZE, "history buffer too small");
-    HIPCHK(c, hipSetDevice(c->device));
-    const pt_ctx::History::Set &s = c->hist.set[c->hist.cur];
-    // (any of the three may be left out; one wait for all)
-    if (colour && need) HIPCHK(c, hipMemcpyAsync(colour, s.h.p, need, hipMemcpyDeviceToHost, c->stream));
-    if (moments && need) HIPCHK(c, hipMemcpyAsync(moments, s.hm.p, need, hipMemcpyDeviceToHost, c->stream));
-    return read_back(c, count, need / 4, s.hn.p, count ? need / 4 : 0, nullptr);
-}
-
-// pt_denoise_guided over the history: its checks in its order, the history for its two state
-// rules, the history's colour, guides and per-pixel count for the accumulation image, the live guides and n.
-int pt_denoise_history(pt_ctx *c, const pt_guided_params *p, int format, void *out, size_t bytes) {
-    if (!c) return PT_ERR_INVALID;
-    if (!p) return fail(c, PT_ERR_INVALID, "null denoise parameters");
-    if (format != PT_DISPLAY_RGBA32F && format != PT_DISPLAY_SRGB8 && format != PT_DENOISE_LINEAR)
-        return fail(c, PT_ERR_INVALID, "bad denoise format");
-    if (p->iterations < 1 || p->iterations > PT_DENOISE_MAX_ITERATIONS)
-        return fail(c, PT_ERR_INVALID, "denoise iterations must be in [1, 8]");
-    if (p->normal_power_log2 > 8) return fail(c, PT_ERR_INVALID, "denoise normal_power_log2 must be in [0, 8]");
-    for (float v : {p->sigma_depth, p->sigma_albedo})
-        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "denoise sigma must be finite and >= 0");
-    if (!std::isfinite(p->sigma_variance) || !(p->sigma_variance > 0.0f))
-        return fail(c, PT_ERR_INVALID, "denoise sigma_variance must be finite and > 0");
-    PtGuided A;
-    std::memset(&A, 0, sizeof A);
-    auto inv_sq = [](float sigma, float scale) {  // (as pt_denoise)
-        if (sigma == 0.0f) return 0.0f;
-        const float v = sigma * scale;
-        const float sq = v * v;
-        return 1.0f / sq;
-    };
-    A.ka = inv_sq(p->sigma_albedo, 1.0f);
-    bool finite = std::isfinite(A.ka);
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        A.kz[i] = inv_sq(p->sigma_depth, std::ldexp(1.0f, int(i)));
-        finite = finite && std::isfinite(A.kz[i]);
-    }
-    if (!finite) return fail(c, PT_ERR_INVALID, "denoise sigma too small: 1 / sigma^2 is not finite");
-    A.sv2 = p->sigma_variance * p->sigma_variance;
-    if (!c->hist.valid) return fail(c, PT_ERR_STATE, kNoHistory);
-    const size_t texels = size_t(c->img.width) * c->img.height;
-    const size_t need = texels * (format == PT_DISPLAY_SRGB8 ? 4 : 16);
-    if (!out || bytes < need) return fail(c, PT_ERR_SIZE, "denoise output buffer too small");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    for (DevBuf &f : c->dn.filter)
-        if ((rc = ensure(c, f, std::max<size_t>(texels * 16, 16))) != PT_OK) return rc;
-    for (DevBuf &v : c->mom.var)
-        if ((rc = ensure(c, v, std::max<size_t>(texels * sizeof(float), 16))) != PT_OK) return rc;
-    if (format != PT_DENOISE_LINEAR && (rc = ensure(c, c->img.display, std::max<size_t>(need, 16))) != PT_OK) return rc;
-    pt_ctx::History &hs = c->hist;
-    const pt_ctx::History::Set &s = hs.set[hs.cur];
-    HIPCHK(c, hs.variance_time.begin(c->stream));
-    pt_launch_history_variance(s.h.as<float>(), s.hm.as<float>(), s.hn.as<float>(), c->mom.var[0].as<float>(), uint32_t(texels),
-                               c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hs.variance_time.end(c->stream));
-    A.g0 = s.g0.as<const float4>();
-    A.g1 = s.g1.as<const float4>();
-    A.w = int32_t(c->img.width);
-    A.h = int32_t(c->img.height);
-    A.npow = int32_t(p->normal_power_log2);
-    // history colour -> filter[0] -> filter[1] ..., variance var[0] -> var[1] -> var[0] ...: the history is only read
-    const float *src = s.h.as<float>();
-    HIPCHK(c, hs.denoise_time.begin(c->stream));
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        A.in = reinterpret_cast<const float4 *>(src);
-        A.out = c->dn.filter[i & 1].as<float4>();
-        A.vin = c->mom.var[i & 1].as<const float>();
-        A.vout = c->mom.var[(i + 1) & 1].as<float>();
-        A.iter = int32_t(i);
-        pt_launch_guided(A, c->dn.lds != 0, c->stream);
-        HIPCHK(c, hipGetLastError());
-        src = c->dn.filter[i & 1].as<float>();
-    }
-    HIPCHK(c, hs.denoise_time.end(c->stream));
-    const void *result = src;
-    if (format != PT_DENOISE_LINEAR) {
-        pt_launch_display(src, c->img.width, c->img.height, format, c->img.display.p, c->stream);
-        HIPCHK(c, hipGetLastError());
-        result = c->img.display.p;
-    }
-    return read_back(c, out, bytes, result, need, nullptr);
 }
 
 int pt_accum_device_ptr(pt_ctx *c, void **dev_ptr, size_t *bytes) {

@@ -313,6 +313,18 @@ class PathTracer:
 
     DENOISE_OUTPUTS = {"linear": N.PT_DENOISE_LINEAR, "display": N.PT_DISPLAY_RGBA32F, "srgb8": N.PT_DISPLAY_SRGB8}
 
+    def _filter(self, fn: str, params, output: str, **fields) -> np.ndarray:
+        """One filter call: the library's ``fn`` with a ``params`` block of
+        ``fields`` (the two counts as int, the sigmas as float), into an image
+        of ``output``'s kind."""
+        if output not in self.DENOISE_OUTPUTS:
+            raise ValueError(f"output must be one of {sorted(self.DENOISE_OUTPUTS)}, got {output!r}")
+        counts = ("iterations", "normal_power_log2")
+        p = params(**{k: int(v) if k in counts else float(v) for k, v in fields.items()})
+        out, po, nbytes = self._image(np.uint8 if output == "srgb8" else np.float32)
+        self._chk(fn, getattr(self._L, fn)(self._ctx, ctypes.byref(p), self.DENOISE_OUTPUTS[output], po, nbytes))
+        return out
+
     def denoise(self, iterations: int = 5, sigma_color: float = 2.0, sigma_depth: float = 0.05,
                 sigma_albedo: float = 0.1, normal_power_log2: int = 5, output: str = "linear") -> np.ndarray:
         """pt_denoise: the accumulation image through ``iterations`` passes of
@@ -322,14 +334,8 @@ class PathTracer:
         "display" / "srgb8" (the result through the display pass, as
         ``display(srgb8=False / True)`` returns it).  A sigma of 0 switches
         its term off."""
-        if output not in self.DENOISE_OUTPUTS:
-            raise ValueError(f"output must be one of {sorted(self.DENOISE_OUTPUTS)}, got {output!r}")
-        p = N.DenoiseParams(iterations=int(iterations), normal_power_log2=int(normal_power_log2),
-                            sigma_color=float(sigma_color), sigma_depth=float(sigma_depth),
-                            sigma_albedo=float(sigma_albedo))
-        out, po, nbytes = self._image(np.uint8 if output == "srgb8" else np.float32)
-        self._chk("pt_denoise", self._L.pt_denoise(self._ctx, ctypes.byref(p), self.DENOISE_OUTPUTS[output], po, nbytes))
-        return out
+        return self._filter("pt_denoise", N.DenoiseParams, output, iterations=iterations, sigma_color=sigma_color,
+                            sigma_depth=sigma_depth, sigma_albedo=sigma_albedo, normal_power_log2=normal_power_log2)
 
     # -- second moments, variance and the variance-guided filter (new) --------
     def read_moments(self) -> np.ndarray:
@@ -381,15 +387,9 @@ class PathTracer:
         a converged pixel keeps its detail and a noisy one is smoothed.  Needs
         ``render_guides`` and valid moments of >= 2 frames; ``output`` as
         ``denoise``.  Both images are left as they are."""
-        if output not in self.DENOISE_OUTPUTS:
-            raise ValueError(f"output must be one of {sorted(self.DENOISE_OUTPUTS)}, got {output!r}")
-        p = N.GuidedParams(iterations=int(iterations), normal_power_log2=int(normal_power_log2),
-                           sigma_variance=float(sigma_variance), sigma_depth=float(sigma_depth),
-                           sigma_albedo=float(sigma_albedo))
-        out, po, nbytes = self._image(np.uint8 if output == "srgb8" else np.float32)
-        self._chk("pt_denoise_guided", self._L.pt_denoise_guided(self._ctx, ctypes.byref(p), self.DENOISE_OUTPUTS[output],
-                                                                  po, nbytes))
-        return out
+        return self._filter("pt_denoise_guided", N.GuidedParams, output, iterations=iterations,
+                            sigma_variance=sigma_variance, sigma_depth=sigma_depth, sigma_albedo=sigma_albedo,
+                            normal_power_log2=normal_power_log2)
 
     def render_until(self, noise: float, max_spp: int, batch: int = 16) -> int:
         """Render "until the noise is below ``noise``": clear the image, switch
@@ -455,15 +455,9 @@ class PathTracer:
         colour, the variance of its moments and per-pixel sample count, and
         its own copy of the guides, so it works after a camera move has made
         the live guides stale.  ``output`` as ``denoise``."""
-        if output not in self.DENOISE_OUTPUTS:
-            raise ValueError(f"output must be one of {sorted(self.DENOISE_OUTPUTS)}, got {output!r}")
-        p = N.GuidedParams(iterations=int(iterations), normal_power_log2=int(normal_power_log2),
-                           sigma_variance=float(sigma_variance), sigma_depth=float(sigma_depth),
-                           sigma_albedo=float(sigma_albedo))
-        out, po, nbytes = self._image(np.uint8 if output == "srgb8" else np.float32)
-        self._chk("pt_denoise_history", self._L.pt_denoise_history(self._ctx, ctypes.byref(p),
-                                                                    self.DENOISE_OUTPUTS[output], po, nbytes))
-        return out
+        return self._filter("pt_denoise_history", N.GuidedParams, output, iterations=iterations,
+                            sigma_variance=sigma_variance, sigma_depth=sigma_depth, sigma_albedo=sigma_albedo,
+                            normal_power_log2=normal_power_log2)
 
     def render_view(self, spp: int, camera: Optional[N.Camera] = None, **accumulate) -> None:
         """One view of an interactive loop in one call: set ``camera`` if one

@@ -68,28 +68,39 @@ def _sq3(v):
     return (v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]
 
 
-def iteration(c, g0, g1, step, kc, kz, ka, npow):
-    """One pass at `step` over colour c (h, w, 4) with guides g0, g1."""
+def _shift(h, w, ox, oy):
+    """(p, q) slices with q = p + (ox, oy) inside an (h, w) image, or None when no p has its q inside."""
+    x0, x1, y0, y1 = max(0, -ox), min(w, w - ox), max(0, -oy), min(h, h - oy)
+    if x0 >= x1 or y0 >= y1:
+        return None
+    return (slice(y0, y1), slice(x0, x1)), (slice(y0 + oy, y1 + oy), slice(x0 + ox, x1 + ox))
+
+
+def iteration(c, g0, g1, step, kc, kz, ka, npow, v=None):
+    """One pass at `step` over colour c (h, w, 4) with guides g0, g1.  kc: the
+    colour constant, one f32 or one per pixel (h, w).  v: a variance plane
+    (h, w) filtered beside the colour with the squared weights (momentref);
+    then (colour, variance) is returned."""
     h, w = c.shape[:2]
     fin = np.isfinite(c[..., :3]).all(-1)
     hit = g1[..., 3]
+    kc = np.broadcast_to(np.asarray(kc, np.float32), (h, w))
     sw = np.zeros((h, w), np.float32)
     sc = np.zeros((h, w, 3), np.float32)
+    sv = np.zeros((h, w), np.float32)
     one = F(1.0)
     for dy in range(-2, 3):
         for dx in range(-2, 3):
-            ox, oy = step * dx, step * dy
-            x0, x1, y0, y1 = max(0, -ox), min(w, w - ox), max(0, -oy), min(h, h - oy)
-            if x0 >= x1 or y0 >= y1:
+            pq = _shift(h, w, step * dx, step * dy)
+            if pq is None:
                 continue  # q is outside the image for every p
-            p = (slice(y0, y1), slice(x0, x1))
-            q = (slice(y0 + oy, y1 + oy), slice(x0 + ox, x1 + ox))
+            p, q = pq
             cq, cp = c[q][..., :3], c[p][..., :3]
             ok = fin[q].copy()
             wgt = np.full(ok.shape, H[abs(dy)] * H[abs(dx)], np.float32)
             if dx != 0 or dy != 0:
                 ok &= hit[q] == hit[p]
-                den = one + _sq3(cq - cp) * kc
+                den = one + _sq3(cq - cp) * kc[p]
                 den_h = den * (one + _sq3(g1[q][..., :3] - g1[p][..., :3]) * ka)
                 dz = g0[q][..., 3] - g0[p][..., 3]
                 den_h = den_h * (one + (dz * dz) * kz)
@@ -104,9 +115,13 @@ def iteration(c, g0, g1, step, kc, kz, ka, npow):
                 ok &= wgt > F(0.0)  # (false for NaN)
             sw[p] = np.where(ok, sw[p] + wgt, sw[p])
             sc[p] = np.where(ok[..., None], sc[p] + wgt[..., None] * cq, sc[p])
+            if v is not None:
+                sv[p] = np.where(ok, sv[p] + (wgt * wgt) * v[q], sv[p])
     out = c.copy()
     out[..., :3] = np.where(fin[..., None], sc / sw[..., None], c[..., :3])
-    return out
+    if v is None:
+        return out
+    return out, np.where(fin, sv / (sw * sw), v).astype(np.float32)
 
 
 def atrous(img, g0, g1, iterations=5, sigma_color=2.0, sigma_depth=0.05, sigma_albedo=0.1, normal_power_log2=5):

@@ -6,8 +6,9 @@ spp = 1 for that frame: the mix's weight is then 1 and the image is the frame
 itself (up to the sign of a zero, which neither A nor c * c keeps).
 frames_fold() mixes such colours into the accumulation image A and the moment
 image M in numpy float32, one IEEE rounding per operation, in frame order.
-guided() is denoiseref's a-trous loop with the per-pixel colour constant and
-the variance plane beside the colour, in the contract's order.
+guided() is denoiseref's a-trous pass (denoiseref.iteration) with the
+per-pixel colour constant and the variance plane beside the colour, in the
+contract's order.
 tests/test_moment_ref.py pins all of it.
 """
 from __future__ import annotations
@@ -79,14 +80,6 @@ def variance(A, M, n):
         return (v[..., 0] + v[..., 1]) + v[..., 2]
 
 
-def _shift(h, w, ox, oy):
-    """(p, q) slices with q = p + (ox, oy) inside an (h, w) image, or None when no p has its q inside."""
-    x0, x1, y0, y1 = max(0, -ox), min(w, w - ox), max(0, -oy), min(h, h - oy)
-    if x0 >= x1 or y0 >= y1:
-        return None
-    return (slice(y0, y1), slice(x0, x1)), (slice(y0 + oy, y1 + oy), slice(x0 + ox, x1 + ox))
-
-
 def smooth3(v):
     """g: the variance plane over each pixel's 3x3 neighbourhood, dy outer, dx
     inner, taps outside the image or not finite left out; +inf where none is left."""
@@ -96,7 +89,7 @@ def smooth3(v):
     sw3 = np.zeros((h, w), np.float32)
     for dy in (-1, 0, 1):
         for dx in (-1, 0, 1):
-            pq = _shift(h, w, dx, dy)
+            pq = D._shift(h, w, dx, dy)
             if pq is None:
                 continue
             p, q = pq
@@ -116,48 +109,6 @@ def noise(A, V, percentile=95.0, owned=None):
     return float(np.percentile(rel[keep], percentile)) if keep.any() else 0.0
 
 
-def iteration(c, v, g0, g1, step, sv2, kz, ka, npow):
-    """One pass at `step` over colour c (h, w, 4) and variance v (h, w): (colour, variance)."""
-    h, w = c.shape[:2]
-    fin = np.isfinite(c[..., :3]).all(-1)
-    hit = g1[..., 3]
-    kc_all = F(1.0) / (sv2 * smooth3(v) + EPS)
-    sw = np.zeros((h, w), np.float32)
-    sc = np.zeros((h, w, 3), np.float32)
-    sv = np.zeros((h, w), np.float32)
-    one = F(1.0)
-    for dy in range(-2, 3):
-        for dx in range(-2, 3):
-            pq = _shift(h, w, step * dx, step * dy)
-            if pq is None:
-                continue
-            p, q = pq
-            cq, cp = c[q][..., :3], c[p][..., :3]
-            ok = fin[q].copy()
-            wgt = np.full(ok.shape, D.H[abs(dy)] * D.H[abs(dx)], np.float32)
-            if dx != 0 or dy != 0:
-                ok &= hit[q] == hit[p]
-                den = one + D._sq3(cq - cp) * kc_all[p]
-                den_h = den * (one + D._sq3(g1[q][..., :3] - g1[p][..., :3]) * ka)
-                dz = g0[q][..., 3] - g0[p][..., 3]
-                den_h = den_h * (one + (dz * dz) * kz)
-                np_, nq = g0[p], g0[q]
-                nd = np.fmax((np_[..., 0] * nq[..., 0] + np_[..., 1] * nq[..., 1]) + np_[..., 2] * nq[..., 2], F(0.0))
-                for _ in range(npow):
-                    nd = nd * nd
-                hit_p = hit[p] != F(0.0)
-                wgt = np.where(hit_p, wgt * nd, wgt)
-                den = np.where(hit_p, den_h, den)
-                wgt = wgt / den
-                ok &= wgt > F(0.0)  # (false for NaN)
-            sw[p] = np.where(ok, sw[p] + wgt, sw[p])
-            sc[p] = np.where(ok[..., None], sc[p] + wgt[..., None] * cq, sc[p])
-            sv[p] = np.where(ok, sv[p] + (wgt * wgt) * v[q], sv[p])
-    out = c.copy()
-    out[..., :3] = np.where(fin[..., None], sc / sw[..., None], c[..., :3])
-    return out, np.where(fin, sv / (sw * sw), v).astype(np.float32)
-
-
 def guided(img, V, g0, g1, iterations=5, sigma_variance=2.0, sigma_depth=0.05, sigma_albedo=0.1, normal_power_log2=5,
            with_variance=False):
     """The filtered image (linear, alpha kept); with_variance: (image, the filtered variance plane)."""
@@ -169,5 +120,6 @@ def guided(img, V, g0, g1, iterations=5, sigma_variance=2.0, sigma_depth=0.05, s
     sv2 = F(sigma_variance) * F(sigma_variance)
     with np.errstate(all="ignore"):
         for i in range(iterations):
-            c, v = iteration(c, v, g0, g1, 1 << i, sv2, kz[i], ka, normal_power_log2)
+            kc = F(1.0) / (sv2 * smooth3(v) + EPS)  # the colour constant of each pixel
+            c, v = D.iteration(c, g0, g1, 1 << i, kc, kz[i], ka, normal_power_log2, v)
     return (c, v) if with_variance else c

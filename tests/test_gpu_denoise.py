@@ -220,6 +220,71 @@ def test_argument_errors(gpu):
     pt.close()
 
 
+def test_refusal_order(gpu):
+    """A call that is wrong in every way at once is refused by the first rule
+    of the list -- null context, null parameters, format, iterations, normal
+    power, sigmas, sigma_variance, a constant that is not finite, state
+    (guides, then moments; or the history), output size -- and, that fault
+    repaired, by the next one, for each of the three filter entry points."""
+    w, h = 24, 16
+    pt = _tracer(w=w, h=h, moments=1)  # no guides, no moments, no history yet
+    L = pt._L
+    buf = np.zeros((h, w, 4), np.float32)
+    vp = buf.ctypes.data_as(ctypes.c_void_p)
+    fns = {name: getattr(L, name) for name in ("pt_denoise", "pt_denoise_guided", "pt_denoise_history")}
+    # every field wrong; then (field, its repair, the refusal it ends) in the order of the rules
+    wrong = dict(iterations=0, normal_power_log2=9, sigma_depth=-1.0, sigma_albedo=1e-30)
+    repairs = [("iterations", 5, "iterations must be in [1, 8]"),
+               ("normal_power_log2", 5, "normal_power_log2 must be in [0, 8]"),
+               ("sigma_depth", 0.05, "sigma must be finite and >= 0")]
+    state = {}  # entry point -> its call, the parameters repaired, the buffer still short
+    for name, fn in fns.items():
+        fixed = name == "pt_denoise"
+        p = N.DenoiseParams(sigma_color=2.0, **wrong) if fixed else N.GuidedParams(sigma_variance=0.0, **wrong)
+
+        def call(fn=fn, ctx=pt._ctx, params=p, fmt=N.PT_DENOISE_LINEAR, nbytes=buf.nbytes - 1):
+            rc = fn(ctx, None if params is None else ctypes.byref(params), fmt, vp, nbytes)
+            return rc, L.pt_last_error(pt._ctx).decode()
+
+        assert call(ctx=None, params=None, fmt=3)[0] == N.PT_ERR_INVALID, name
+        rc, msg = call(params=None, fmt=3)
+        assert rc == N.PT_ERR_INVALID and "null denoise parameters" in msg, (name, rc, msg)
+        rc, msg = call(fmt=3)
+        assert rc == N.PT_ERR_INVALID and "bad denoise format" in msg, (name, rc, msg)
+        for field, good, text in repairs:
+            rc, msg = call()
+            assert rc == N.PT_ERR_INVALID and text in msg, (name, field, rc, msg)
+            setattr(p, field, good)
+        if not fixed:
+            rc, msg = call()
+            assert rc == N.PT_ERR_INVALID and "sigma_variance must be finite and > 0" in msg, (name, rc, msg)
+            p.sigma_variance = 2.0
+        rc, msg = call()
+        assert rc == N.PT_ERR_INVALID and "1 / sigma^2 is not finite" in msg, (name, rc, msg)
+        p.sigma_albedo = 0.1
+        state[name] = call
+    # the state rules, each repaired in turn; the short buffer answers last
+    guides, variance, history, size = "guides stale", "no variance", "no history", "output buffer too small"
+
+    def expect(**want):
+        got = {name: call() for name, call in state.items()}
+        for name, (code, text) in want.items():
+            assert got[name][0] == code and text in got[name][1], (name, got[name], code, text)
+
+    S, Z = N.PT_ERR_STATE, N.PT_ERR_SIZE
+    expect(pt_denoise=(S, guides), pt_denoise_guided=(S, guides), pt_denoise_history=(S, history))
+    pt.render_guides()
+    expect(pt_denoise=(Z, size), pt_denoise_guided=(S, variance), pt_denoise_history=(S, history))
+    pt.dispatch(G.constants(w, h, frame=1, last_clear=0), 2)
+    expect(pt_denoise=(Z, size), pt_denoise_guided=(Z, size), pt_denoise_history=(S, history))
+    pt.accumulate_history()
+    expect(pt_denoise=(Z, size), pt_denoise_guided=(Z, size), pt_denoise_history=(Z, size))
+    assert not buf.any()  # nothing was written
+    for name, call in state.items():
+        assert call(nbytes=buf.nbytes)[0] == N.PT_OK, name
+    pt.close()
+
+
 def test_it_denoises_and_times(gpu):
     """C3 with a sky at 96x54: the denoised 4-spp image (default parameters) is
     closer to the 1024-spp image than the raw 4-spp image is."""
