@@ -158,6 +158,10 @@ int ensure_bin(pt_ctx *c, size_t samples, size_t passes, int lanes) {
     return PT_OK;
 }
 
+#ifndef PT_SCATTER_ITEMS  // slots per thread of a scatter tile (BinPlan::scatter_grid; an A/B build may set it)
+#define PT_SCATTER_ITEMS 16
+#endif
+
 // What every chunk of one dispatch shares.
 struct BinPlan {
     uint32_t n_pix = 0, spp = 0, F = 0;  // (F: frames per chunk)
@@ -437,10 +441,8 @@ int encode_chunk(pt_ctx *c, const BinPlan &pl, const PtLaunch &L, uint32_t done,
     Fp.L.spp = int32_t(fr);
     Fp.color = b.color.as<float4>();
     Fp.frames = int32_t(fr);
-    Fp.lanes = nl;  // (the colour regions' split: bin_fold_body)
-    const unsigned fold_grid = unsigned((pl.n_pix + PT_BIN_BLOCK - 1) / PT_BIN_BLOCK);
-    if (pl.moments) pt_launch_bin_fold_m(Fp, pl.moments, fold_grid, c->stream);
-    else pt_launch_bin(PtBinStage::Fold, Fp, pl.stats, fold_grid, c->stream);
+    Fp.lanes = nl;  // (the colour regions' split: pt_bin_kernels.hip fold_body)
+    pt_launch_bin_fold(Fp, pl.moments, unsigned((pl.n_pix + PT_BIN_BLOCK - 1) / PT_BIN_BLOCK), c->stream);
     HIPCHK(c, hipGetLastError());
     return PT_OK;
 }

@@ -27,6 +27,15 @@
 //
 // Paths are independent and the fold runs in frame order, so the schedule
 // changes nothing in the image: it is bit-identical to the other kernels.
+//
+// This header holds what a scene kernel can compile: the ray record, the pass
+// block (PtPass), the bin of a check[] set, bounds(), and the bodies of the
+// gen, shade and trace passes, which are templates over the map type.  Every
+// scene's runtime-compiled source includes it (build.py EMBED) and its text
+// is part of the scene kernels' cache key.  The passes that evaluate no map()
+// -- scan, scatter, sky and fold -- have no scene build and are written as
+// kernels in pt_bin_kernels.hip, with the interpreter's instances of the
+// three bodies here.
 #pragma once
 
 #include "pt_path.h"
@@ -46,9 +55,6 @@
 #endif
 #define PT_CTRL_CURSOR(k) (32u * (1u + uint32_t(k)))
 #define PT_CTRL_STRIDE (32u * (1u + uint32_t(PT_RUN_SHARDS)))
-#ifndef PT_SCATTER_ITEMS
-#define PT_SCATTER_ITEMS 16
-#endif
 
 // A path between two segments (ray) or, taps in the trace pass, at the hit
 // of its segment (hit record), 64 B = four 16 B quads:
@@ -153,7 +159,7 @@ struct PtPass {
     float4 *hitn;           // trace -> shade: check[] bits 64..127 of a hit (.zw; scenes with > 64 entries)
     unsigned long long *btab;  // [PT_BINS] check[] set + 1 per bin (0: free), null: hashed bins (bin_resolve);
                                // [PT_BINS]: sets that found no slot (the dispatch's overflow count)
-    int32_t lanes;          // fold: pipelines that split the chunk's frames (colour regions, bin_fold_body)
+    int32_t lanes;          // fold: pipelines that split the chunk's frames (colour regions, fold_body)
     uint32_t n_src_const;
     int32_t bounce;         // segment index of this pass (path_trace's loop counter i)
     int32_t n_pix;          // local pixel slots: n_tiles * 64
@@ -659,94 +665,6 @@ __device__ __forceinline__ void bin_shade_body(const PtPass &P) {
     if constexpr (!TAPS) flush_stats<ST>(L, stt, PT_ST_COUNT);
 }
 
-// scan: exclusive prefix of the histogram; clears the histogram and this
-// pass's cursors.  One wave (PT_SCAN_THREADS lanes, PT_BINS / 64 bins each,
-// no LDS): it fits on a CU beside the other pipeline's persistent trace
-// waves (28 of 32 slots), where a 1024-thread block waited for that trace
-// pass to drain (1.26 ms per launch with two pipelines, 5 us alone).
-#define PT_SCAN_THREADS 64
-__device__ __forceinline__ void bin_scan_body(const PtPass &P) {
-    constexpr int PER = PT_BINS / PT_SCAN_THREADS;
-    const int t = int(threadIdx.x);
-    uint4 *h4 = reinterpret_cast<uint4 *>(P.hist + t * PER);
-    uint4 *o4 = reinterpret_cast<uint4 *>(P.offs + t * PER);
-    uint32_t sum = 0u;
-#pragma unroll
-    for (int j = 0; j < PER / 4; ++j) {
-        const uint4 v = h4[j];
-        sum += v.x + v.y + v.z + v.w;
-    }
-    uint32_t inc = sum;  // inclusive prefix over the wave's lanes
-#pragma unroll
-    for (int off = 1; off < PT_SCAN_THREADS; off <<= 1) {
-        const uint32_t x = uint32_t(__shfl_up(int(inc), off, PT_SCAN_THREADS));
-        if (t >= off) inc += x;
-    }
-    uint32_t run = inc - sum;
-#pragma unroll
-    for (int j = 0; j < PER / 4; ++j) {
-        const uint4 v = h4[j];
-        uint4 o;
-        o.x = run;
-        run += v.x;
-        o.y = run;
-        run += v.y;
-        o.z = run;
-        run += v.z;
-        o.w = run;
-        run += v.w;
-        o4[j] = o;
-        h4[j] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (t == PT_SCAN_THREADS - 1) P.ctrl[0] = inc;
-    if (t < PT_RUN_SHARDS) P.ctrl[PT_CTRL_CURSOR(t)] = 0u;
-}
-
-// scatter: ray slots into bin order.  Per block tile, the slots of one bin
-// take consecutive places (LDS ranks) after one global reservation.
-__device__ __forceinline__ void bin_scatter_body(const PtPass &P) {
-    __shared__ uint32_t cnt[PT_BINS];
-    const uint32_t n = P.n_src ? *P.n_src : P.n_src_const;
-    // One contiguous run of the slots per block: count its bins in LDS,
-    // reserve each bin's places with one global atomic for the whole run
-    // (not one per 4096-slot tile), then read the keys again and hand out
-    // the places with LDS cursors.
-    const uint32_t per = ((n + gridDim.x - 1u) / gridDim.x + PT_BIN_BLOCK - 1u) & ~uint32_t(PT_BIN_BLOCK - 1);
-    const uint32_t b0 = min(n, blockIdx.x * per), b1 = min(n, b0 + per);
-    // (eight keys in flight per thread: the loads are issued before the LDS
-    // atomics that use them)
-    constexpr uint32_t U = 8u;
-    hist_zero(cnt);
-    for (uint32_t e0 = b0 + threadIdx.x; e0 < b1; e0 += U * PT_BIN_BLOCK) {
-        uint32_t k[U];
-#pragma unroll
-        for (uint32_t j = 0; j < U; ++j) {
-            const uint32_t e = e0 + j * PT_BIN_BLOCK;
-            k[j] = e < b1 ? P.key[e] : PT_BIN_NONE;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < U; ++j)
-            if (k[j] != PT_BIN_NONE) atomicAdd(&cnt[k[j]], 1u);
-    }
-    __syncthreads();
-    for (int b = int(threadIdx.x); b < PT_BINS; b += PT_BIN_BLOCK) {
-        const uint32_t c = cnt[b];
-        if (c != 0u) cnt[b] = atomicAdd(&P.offs[b], c);
-    }
-    __syncthreads();
-    for (uint32_t e0 = b0 + threadIdx.x; e0 < b1; e0 += U * PT_BIN_BLOCK) {
-        uint32_t k[U];
-#pragma unroll
-        for (uint32_t j = 0; j < U; ++j) {
-            const uint32_t e = e0 + j * PT_BIN_BLOCK;
-            k[j] = e < b1 ? P.key[e] : PT_BIN_NONE;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < U; ++j)
-            if (k[j] != PT_BIN_NONE) P.idx[atomicAdd(&cnt[k[j]], 1u)] = e0 + j * PT_BIN_BLOCK;
-    }
-}
-
 // trace: one wave per block, persistent.  The wave takes runs of the binned
 // slots (so its lanes share their check[] set).  Windows of 64: the slots of
 // the next window are loaded one window ahead, the current window's rays are
@@ -900,7 +818,7 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
                     const pt_f3 c = final_color(L.debug, P.bounce, L.bounces, pt_f3{0.0f, 0.0f, 0.0f});
                     P.color[sid] = make_float4(c.x, c.y, c.z, 0.0f);
                 }
-                // (.x: the traced ray's slot, for the sky pass -- pt_kernel.hip pt_bin_sky_kernel)
+                // (.x: the traced ray's slot, for the sky pass -- pt_bin_kernels.hip pt_bin_sky_kernel)
                 if constexpr (TAPS) P.rout[pos].q[2] = rec_miss(slot, sid);
                 else P.hq[pos] = hq_miss(slot);
                 if constexpr (GEN) P.color[sid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (no gen pass zeroed it)
@@ -1027,60 +945,6 @@ __device__ __forceinline__ void bin_trace_body(const PtPass &P) {
     }
     (void)st.lap(PT_ST_CYC_TOTAL, t_start);
     flush_stats<ST>(L, st);
-}
-
-// fold: every pixel mixes its frames in order (test_compute.glsl:240-245).
-#define PT_FOLD_SLICE 8  // frames per LDS slice of the fold
-__device__ __forceinline__ void bin_fold_body(const PtPass &P) {
-    // A block folds PT_BIN_BLOCK consecutive local pixels.  Each pipeline's
-    // colour region holds its frames as [pixel][frame], so the block's
-    // pixels' next PT_FOLD_SLICE frames are runs of PT_FOLD_SLICE float4 per
-    // pixel: the block loads them together (8 threads per 128 B run) into
-    // LDS, then each thread mixes its pixel's frames in frame order.
-    __shared__ float4 tile[PT_BIN_BLOCK][PT_FOLD_SLICE + 1];  // (+1: no bank conflicts between rows)
-    const PtLaunch &L = P.L;
-    const uint32_t t = threadIdx.x, pl0 = blockIdx.x * PT_BIN_BLOCK, pl = pl0 + t;
-    const uint32_t npix = uint32_t(P.n_pix), fr = uint32_t(P.frames);
-    const uint32_t nl = uint32_t(P.lanes > 0 ? P.lanes : 1);
-    int x = 0, y = 0;
-    bool mine = pl < npix && L.write;
-    if (mine) {
-        pixel_of(L, pl, x, y);
-        mine = x < L.width && y < L.height;
-    }
-    float4 *texel = mine ? accum_texel(L, x, y) : nullptr;
-    if (L.debug != 0) {  // direct store of the chunk's (single) frame: one pipeline, one frame
-        if (mine) {
-            const float4 c = P.color[pl];
-            accum_store(texel, c.x, c.y, c.z);
-        }
-        return;
-    }
-    float ar = 0.0f, ag = 0.0f, ab = 0.0f;
-    if (mine) accum_load(texel, ar, ag, ab);  // (mine holds L.write; the debug views have returned)
-    uint32_t f0 = 0u;  // the chunk frame of region j's first frame
-    for (uint32_t j = 0u; j < nl; ++j) {
-        const uint32_t fl = fr / nl + (j < fr % nl ? 1u : 0u);
-        const float4 *reg = P.color + size_t(f0) * npix;
-        for (uint32_t s0 = 0u; s0 < fl; s0 += PT_FOLD_SLICE) {
-            const uint32_t sn = fl - s0 < PT_FOLD_SLICE ? fl - s0 : PT_FOLD_SLICE;
-            __syncthreads();  // (the previous slice's reads are done)
-            for (uint32_t e = t; e < PT_BIN_BLOCK * PT_FOLD_SLICE; e += PT_BIN_BLOCK) {
-                const uint32_t q = e / PT_FOLD_SLICE, k = e % PT_FOLD_SLICE;
-                if (k < sn && pl0 + q < npix) tile[q][k] = reg[size_t(pl0 + q) * fl + s0 + k];
-            }
-            __syncthreads();
-            if (mine) {
-                for (uint32_t k = 0u; k < sn; ++k) {
-                    const float4 c = tile[t][k];
-                    const int32_t lc = int32_t(uint32_t(L.last_clear0) + f0 + s0 + k);
-                    mix_frame(ar, ag, ab, pt_f3{c.x, c.y, c.z}, lc);
-                }
-            }
-        }
-        f0 += fl;
-    }
-    if (mine) accum_store(texel, ar, ag, ab);
 }
 
 }  // namespace pt

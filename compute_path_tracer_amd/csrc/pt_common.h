@@ -1,5 +1,5 @@
 // pt_common.h -- device building blocks shared by the ahead-of-time kernels
-// (pt_kernel.hip) and the per-scene kernels compiled at run time with hipRTC
+// (pt_kernel.hip, pt_bin_kernels.hip) and the per-scene kernels compiled at run time with hipRTC
 // (pt_jit.cpp).  One definition of every f32 expression, so the AOT
 // interpreter, the JIT-specialised map() and the oracle stay bit-identical.
 #pragma once

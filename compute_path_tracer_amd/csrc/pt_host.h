@@ -12,15 +12,21 @@
 #include "pt_binned.h"
 #include "pt_device.h"
 
-// ahead-of-time scene kernels (pt_kernel.hip; the image-space kernels' launches are in pt_post.h)
+// ahead-of-time scene kernels (pt_kernel.hip; the image-space kernels' launches are in pt_post.h).  moments: the
+// simple kernel also mixes each frame's squared colour into the moment image (pt_set_option "moments", DESIGN.md
+// 3.28; debug 0, write 1 only), nullptr: the simple or the wave kernel as L asks
 bool pt_use_simple_kernel(const PtLaunch &L);
-void pt_launch_render(const PtLaunch &L, bool stats, hipStream_t stream);
-enum class PtBinStage { Gen, Shade, Scan, Scatter, Trace, Fold };
+void pt_launch_render(const PtLaunch &L, bool stats, float *moments, hipStream_t stream);
+// the binned pipeline's ahead-of-time kernels (pt_bin_kernels.hip)
+enum class PtBinStage { Gen, Shade, Scan, Scatter, Trace };
 void pt_launch_bin(PtBinStage stage, const PtPass &P, bool stats, unsigned grid, hipStream_t stream);
 int pt_bin_trace_blocks_per_cu(bool stats);  // occupancy of the interpreter trace kernel
 // the sky pass after a binned trace pass (pt_set_sky): P as that trace pass's shade pass takes it; quads: the
 // trace pass wrote hit quads (taps in the shade pass), not hit records
 void pt_launch_bin_sky(const PtPass &P, bool quads, unsigned grid, hipStream_t stream);
+// the fold of a chunk; moments: it also keeps the moment image (as pt_launch_render; pt_bin_fold_m_kernel instead
+// of pt_bin_fold_kernel), nullptr: the plain fold
+void pt_launch_bin_fold(const PtPass &P, float *moments, unsigned grid, hipStream_t stream);
 // the denoiser's guide images (pt_render_guides): L as a dispatch takes it, over every tile, a lens as its pinhole
 void pt_launch_guides(const PtLaunch &L, float *g0, float *g1, hipStream_t stream);
 // ray queries (pt_trace_rays / pt_pick_pixels): L as pt_launch_guides takes it; device pointers, any
@@ -33,11 +39,6 @@ void pt_launch_rays(const PtLaunch &L, const float *ro, const float *rd, uint32_
                     hipStream_t stream);
 void pt_launch_pick(const PtLaunch &L, const int32_t *xy, uint32_t n, float *t, int32_t *shape, float *normal,
                     hipStream_t stream);
-// second moments (pt_set_option "moments"): the simple kernel and the binned fold that also mix
-// each frame's squared colour into the moment image (debug 0, write 1 only; launched instead of pt_render_kernel /
-// pt_bin_fold_kernel while the option is on)
-void pt_launch_render_m(const PtLaunch &L, float *moments, hipStream_t stream);
-void pt_launch_bin_fold_m(const PtPass &P, float *moments, unsigned grid, hipStream_t stream);
 
 // Expand (program, data[]) into the device tables (see pt_device.h).
 int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, const float *data, uint32_t n,

@@ -1,6 +1,8 @@
 // pt_pixel.h -- what the scene-side per-pixel kernels (pt_kernel.hip: guides,
 // picks) and the image-space kernels (pt_post.hip: temporal accumulation, the
-// filters) both state: a pixel's jitter-free primary ray and the finite tests.
+// filters) both state: a pixel's jitter-free primary ray and the finite tests;
+// and what the simple kernel (pt_kernel.hip) and the binned fold
+// (pt_bin_kernels.hip) both state: a frame's second moments.
 // Ahead-of-time only: no hipRTC scene source includes it, so it is not among
 // the embedded headers (build.py EMBED) and no scene kernel's cache key sees it.
 #pragma once
@@ -13,6 +15,16 @@ __device__ __forceinline__ bool pt_finite_f(float v) { return (__float_as_uint(v
 __device__ __forceinline__ bool pt_finite_rgb(const float4 &c) {
     return (__float_as_uint(c.x) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(c.y) & 0x7f800000u) != 0x7f800000u &&
            (__float_as_uint(c.z) & 0x7f800000u) != 0x7f800000u;
+}
+
+// Second moments (pt_set_option "moments"): a frame's squared
+// colour into the moment texel, with mix_frame's own w and 1 - w; the moment
+// texel is the accumulation texel's place in the moment image.
+__device__ __forceinline__ void mix_moment(float &mr, float &mg, float &mb, const pt_f3 &c, int32_t last_clear) {
+    pt::mix_frame(mr, mg, mb, pt_f3{c.x * c.x, c.y * c.y, c.z * c.z}, last_clear);
+}
+__device__ __forceinline__ float4 *moment_texel(const PtLaunch &L, float *moments, const float4 *texel) {
+    return reinterpret_cast<float4 *>(moments) + (texel - reinterpret_cast<const float4 *>(L.accum));
 }
 
 // The jitter-free primary ray of pixel (x, y) under a camera: calc_uv without

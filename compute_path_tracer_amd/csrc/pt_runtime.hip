@@ -239,21 +239,20 @@ int pt_get_sky(const pt_ctx *c, pt_sky *out, int *is_off) {
 static bool use_binned(const PtLaunch &L) { return L.kernel == PT_KERNEL_BINNED && !pt_use_simple_kernel(L); }
 
 // Launch one chunk: the scene-specialised wavefront kernel when loaded, else
-// the ahead-of-time kernels (pt_kernel.hip).
+// the ahead-of-time kernels (pt_kernel.hip, pt_bin_kernels.hip).
 // moments: the launch also keeps the moment image (pt_dispatch: a path-traced
-// writing launch of the binned pipeline or the simple kernel, nothing else).
+// writing launch of the binned pipeline or the simple kernel, nothing else --
+// so never one of the wave kernel).
 static int launch(pt_ctx *c, PtLaunch &L, bool stats, float *moments = nullptr) {
-    if (use_binned(L)) return pt_launch_binned(c, L, stats, moments);
     const PtJitModule *jm = pt_jit_active(c->jit);
-    if (moments) {
-        pt_launch_render_m(L, moments, c->stream);
-        HIPCHK(c, hipGetLastError());
+    if (use_binned(L)) {
+        return pt_launch_binned(c, L, stats, moments);
     } else if (!pt_use_simple_kernel(L) && jm) {
         void *args[] = {&L};
         HIPCHK(c, hipModuleLaunchKernel(pt_jit_select(*jm, PtJitStage::Render, stats, false, false, false),
                                         unsigned(L.n_tiles), 1, 1, 64, 1, 1, 0, c->stream, args, nullptr));
     } else {
-        pt_launch_render(L, stats, c->stream);
+        pt_launch_render(L, stats, moments, c->stream);
         HIPCHK(c, hipGetLastError());
     }
     return PT_OK;
