@@ -123,3 +123,57 @@ def first_difference(got, want):
 def pixels_changed(a, b):
     """Pixels whose bits differ between two oracle images."""
     return int((bits(a) != bits(b)).any(-1).sum())
+
+
+def assert_same(got, want, what):
+    """Bit equality of two arrays of one shape and type (float32 by its bits: a
+    NaN equals only the same NaN), the failure naming `what`, how many values
+    differ and the first one."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype}{got.shape}, want {want.dtype}{want.shape}"
+    same = bits(got) == bits(want) if got.dtype == np.float32 else got == want
+    if not same.all():
+        at = tuple(int(v) for v in np.argwhere(~same)[0])
+        raise AssertionError(f"{what}: {int((~same).sum())} of {same.size} values differ, first at {at}: "
+                             f"got {got[at]!r} want {want[at]!r}")
+
+
+def refused(fn, *args, **kw):
+    """(code, message) of the NativeError the call must raise."""
+    try:
+        fn(*args, **kw)
+    except N.NativeError as e:
+        return e.code, str(e)
+    raise AssertionError(f"{getattr(fn, '__name__', fn)} was not refused")
+
+
+def shape_albedo(prog, data, shape):
+    """The albedo of the product's shape ordinals under `prog` with `data` (black for -1), float32 [n][3]."""
+    from compute_path_tracer_amd.mesh import Mesh
+
+    s = np.asarray(shape, np.int32).reshape(-1)
+    return Mesh(np.zeros((len(s), 3)), np.zeros((len(s), 3)), s, np.zeros((0, 3))).vertex_colors(prog, data)
+
+
+def assert_queries(pt, scene, guides, picks, what):
+    """id_image() of `pt` bit for bit against the expected guide planes
+    (g0, g1) and, where `picks` is given, against rayref.pick's (t, node,
+    normal) of every pixel.  scene: (program, data, rows); a shape number is
+    compared through its albedo, as test_gpu_rays.py does."""
+    import meshref
+
+    prog, data, rows = scene
+    g0, g1 = guides
+    h, w = g0.shape[:2]
+    got = pt.id_image()
+    albedo = shape_albedo(prog, data, got.shape).reshape(h, w, 3)
+    assert_same(got.t, g0[..., 3], f"{what}: id_image t against g0")
+    assert_same(got.normal, g0[..., :3], f"{what}: id_image normal against g0")
+    assert_same(got.hit.astype(np.float32), g1[..., 3], f"{what}: id_image hit against g1")
+    assert_same(albedo, g1[..., :3], f"{what}: id_image shape's albedo against g1")
+    if picks is not None:
+        t, node, nrm = picks
+        assert_same(got.t, t, f"{what}: id_image t against rayref.pick")
+        assert_same(got.normal, nrm, f"{what}: id_image normal against rayref.pick")
+        assert_same(albedo, meshref.node_albedo(rows, node).reshape(h, w, 3), f"{what}: shape against rayref.pick")
+        assert np.array_equal(got.hit, ~(t > np.float32(100.0))), f"{what}: hit against rayref.pick"
