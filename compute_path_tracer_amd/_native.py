@@ -98,7 +98,15 @@ class TemporalParams(Structure):
 
 
 PT_MESH_BRICK, PT_MESH_MAX_CELLS, PT_MESH_MAX_PROJECT = 8, 1024, 8
-PT_RAYS_MAX = 1 << 26  # rays or pixels per pt_trace_rays / pt_pick_pixels call
+PT_RAYS_MAX = 1 << 26  # rays or pixels per pt_trace_rays / pt_pick_pixels / pt_trace_radiance call
+PT_RADIANCE_RAY, PT_RADIANCE_HEMISPHERE = 0, 1  # pt_radiance_params.mode
+PT_RADIANCE_MAX_SPP = 65536
+
+
+class RadianceParams(Structure):
+    """pt_radiance_params: the samples, stream, depth and mode of ``pt_trace_radiance`` (new)."""
+
+    _fields_ = [("spp", c_uint32), ("sample0", c_uint32), ("seed", c_uint32), ("bounces", c_int32), ("mode", c_int32)]
 
 
 class MeshDesc(Structure):
@@ -153,7 +161,7 @@ class Aabb(Structure):
 assert ctypes.sizeof(Constants) == 16 and ctypes.sizeof(Settings) == 20
 assert ctypes.sizeof(Camera) == 56 and ctypes.sizeof(Sky) == 52 and ctypes.sizeof(DenoiseParams) == 20
 assert ctypes.sizeof(GuidedParams) == 20 and ctypes.sizeof(TemporalParams) == 16
-assert ctypes.sizeof(MeshDesc) == 36 and ctypes.sizeof(MeshInfo) == 48
+assert ctypes.sizeof(MeshDesc) == 36 and ctypes.sizeof(MeshInfo) == 48 and ctypes.sizeof(RadianceParams) == 20
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
 
@@ -225,6 +233,7 @@ SIGNATURES = {
     "pt_trace_rays": (c_int, [_ctx, _f32p, _f32p, c_uint32, _f32p, POINTER(c_int32), _f32p]),
     "pt_pick_pixels": (c_int, [_ctx, POINTER(Constants), POINTER(Settings), POINTER(c_int32), c_uint32, _f32p,
                                POINTER(c_int32), _f32p]),
+    "pt_trace_radiance": (c_int, [_ctx, _f32p, _f32p, c_uint32, POINTER(RadianceParams), _f32p, _f32p]),
     "pt_probe_map": (c_int, [_ctx, c_int, c_int, c_uint32, _f32p, _u64p, _f32p, _u64p, c_int, _f32p, POINTER(c_int32),
                              _u64p, _u64p]),
     "pt_probe_taps": (c_int, [_ctx, c_int, c_uint32, _f32p, _u64p, _f32p, _f32p, POINTER(c_int32), _u64p, _u64p]),

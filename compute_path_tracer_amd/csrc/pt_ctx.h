@@ -248,6 +248,16 @@ struct pt_ctx {
         DevBuf ro, rd, xy, t, shape, normal;
         TimedSection rays_time, pick_time;
     } rays;
+    // radiance queries (pt_trace_radiance): the staging of a call's rays and of their running mean
+    // and moment (12 B per ray each), and a chunk's shared first hits (32 B per ray) and colours (16 B per sample, at
+    // most `samples` of them in flight), grown on first use; the summed device time of the last call's kernels (a
+    // pair of events per chunk) and of its first-segment kernels alone
+    struct Radiance {
+        DevBuf ro, rd, mean, moment, first, colour;
+        int samples = 1 << 22;  // pt_set_option "radiance_samples"
+        EventLog klog, flog;
+        size_t bytes() const { return ro.cap + rd.cap + mean.cap + moment.cap + first.cap + colour.cap; }
+    } rad;
     // the probes (pt_probe_map / pt_probe_taps / pt_probe_bounds, pt_map_probe.hip): the probe
     // modules loaded so far by their generated source, how many were compiled and in how many seconds, and the
     // staging of a call's inputs and outputs, grown on first use

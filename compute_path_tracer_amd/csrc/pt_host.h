@@ -39,6 +39,24 @@ void pt_launch_rays(const PtLaunch &L, const float *ro, const float *rd, uint32_
                     hipStream_t stream);
 void pt_launch_pick(const PtLaunch &L, const int32_t *xy, uint32_t n, float *t, int32_t *shape, float *normal,
                     hipStream_t stream);
+// radiance queries (pt_trace_radiance): one chunk of a call, whole rays.  L as a dispatch takes it
+// (the sky kept), bounces the call's.  Three launches on `stream`: first (PT_RADIANCE_RAY only) marches each ray's
+// first segment once into `first`; samples runs one path per (ray, sample) into `colour`; fold mixes each ray's
+// colours in sample order into mean / moment.  Device pointers throughout.
+#ifndef PT_RADIANCE_RAY_FASTEST    // (an A/B build may set it: build.build_variant)
+#define PT_RADIANCE_RAY_FASTEST 0  // 0: a wave's lanes are successive samples of a ray; 1: successive rays of a sample (EXPERIMENTS.md)
+#endif
+struct PtRadiance {
+    const float *ro, *rd;  // [n][3], every ray of the call
+    float4 *first;         // [rays][2] of the chunk: {hit point, t}, {tap differences, material index or -1: not traced}
+    float4 *colour;        // [rays][spp] of the chunk
+    float *mean, *moment;  // [n][3], in / out; either nullptr
+    uint32_t ray0, rays;   // the chunk's first ray in the call, and its ray count (rays * spp < 2^31)
+    uint32_t spp, sample0, seed;
+    int32_t mode;          // PT_RADIANCE_*
+};
+enum class PtRadianceStage { First, Samples, Fold };
+void pt_launch_radiance(PtRadianceStage stage, const PtLaunch &L, const PtRadiance &R, hipStream_t stream);
 
 // Expand (program, data[]) into the device tables (see pt_device.h).
 int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, const float *data, uint32_t n,

@@ -120,6 +120,8 @@ const Option kOptions[] = {
     OPT_INT("shade_taps", bin.shade_taps, 0, 1, "shade_taps must be 0 or 1"),
     OPT_INT("denoise_lds", dn.lds, 0, 1, "denoise_lds must be 0 or 1"),
     OPT_INT("mesh_skip", mesh.skip, 0, 1, "mesh_skip must be 0 or 1"),
+    // samples in flight per chunk of a pt_trace_radiance call: at least one ray of PT_RADIANCE_MAX_SPP samples
+    OPT_INT("radiance_samples", rad.samples, PT_RADIANCE_MAX_SPP, 1 << 28, "radiance_samples must be in [65536, 2^28]"),
     // set through its own setter (the moment image comes and goes with it), read as it is
     {"moments", nullptr, 0, 0, nullptr, set_moments,
      [](pt_ctx *c, const char *, double *v) { return int((*v = double(c->mom.on), PT_OK)); }, false},
@@ -173,6 +175,11 @@ const Option kOptions[] = {
     // the last pt_trace_rays' / pt_pick_pixels' kernel (both calls waited for it)
     OPT_GET("rays_ms", section_ms(c, c->rays.rays_time, false, v)),
     OPT_GET("pick_ms", section_ms(c, c->rays.pick_time, false, v)),
+    // the last pt_trace_radiance's kernels, summed over its chunks (the call waited for them), and the shared
+    // first segments' part of that (0 in hemisphere mode); the device memory its staging holds
+    OPT_GET("radiance_ms", log_ms(c, c->rad.klog, v)),
+    OPT_GET("radiance_first_ms", log_ms(c, c->rad.flog, v)),
+    OPT_READ("radiance_bytes", c->rad.bytes()),
     OPT_READ("guides_valid", c->dn.guides_valid ? 1.0 : 0.0),
     // second moments: whether the moment image and the accumulation image are one render's, and of how many frames;
     // the last variance kernel, and all iterations of the last pt_denoise_guided (without its variance and display passes)

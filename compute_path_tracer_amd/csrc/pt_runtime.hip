@@ -535,6 +535,77 @@ int pt_pick_pixels(pt_ctx *c, const pt_constants *k, const pt_settings *s, const
     return query_read_back(c, n, t, shape, normal);
 }
 
+// ---- radiance queries ---------------------------------------------
+// The launch block is a dispatch's (make_launch): debug 0, so the sky is kept; bounces from p; the image is not
+// written (none of these kernels reads the flag or the image).  The rays are walked in chunks of whole rays, at
+// most "radiance_samples" samples in flight: the colours and the shared first hits are a chunk's, the rays, the
+// means and the moments the call's.
+int pt_trace_radiance(pt_ctx *c, const float *ro, const float *rd, uint32_t n, const pt_radiance_params *p, float *mean,
+                      float *moment) {
+    if (!c) return PT_ERR_INVALID;
+    if (!p) return fail(c, PT_ERR_INVALID, "null radiance parameters");
+    if (n > PT_RAYS_MAX) return fail(c, PT_ERR_INVALID, "more than PT_RAYS_MAX rays");
+    if (n && (!ro || !rd)) return fail(c, PT_ERR_INVALID, "null ray origins / directions");
+    if (p->spp < 1 || p->spp > PT_RADIANCE_MAX_SPP) return fail(c, PT_ERR_INVALID, "spp outside [1, PT_RADIANCE_MAX_SPP]");
+    if (uint64_t(p->sample0) + uint64_t(p->spp) > (1ull << 24)) return fail(c, PT_ERR_INVALID, "sample0 + spp beyond 1 << 24");
+    if (p->bounces < 0) return fail(c, PT_ERR_INVALID, "negative bounces");
+    if (p->mode != PT_RADIANCE_RAY && p->mode != PT_RADIANCE_HEMISPHERE) return fail(c, PT_ERR_INVALID, "bad radiance mode");
+    if (p->sample0 > 0 && (!mean || !moment)) return fail(c, PT_ERR_INVALID, "a continuation (sample0 > 0) needs mean and moment");
+    const pt_constants k = {0.0f, 0, 1.0f, 0};  // (a query reads no constants: the launch block wants some)
+    const pt_settings s = {0, p->bounces, 1.0f, 1.0f, 0};
+    PtLaunch L;
+    int rc = make_launch(c, &k, &s, 1, L);
+    if (rc != PT_OK) return rc;
+    L.write = 0;
+    if (!n) return PT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    pt_ctx::Radiance &r = c->rad;
+    const uint32_t chunk_rays = std::min<uint32_t>(n, std::max<uint32_t>(1u, uint32_t(r.samples) / p->spp));
+    const bool shared = p->mode == PT_RADIANCE_RAY;
+    if ((rc = ensure(c, r.ro, size_t(n) * 12)) != PT_OK) return rc;
+    if ((rc = ensure(c, r.rd, size_t(n) * 12)) != PT_OK) return rc;
+    if ((mean || p->sample0) && (rc = ensure(c, r.mean, size_t(n) * 12)) != PT_OK) return rc;
+    if ((moment || p->sample0) && (rc = ensure(c, r.moment, size_t(n) * 12)) != PT_OK) return rc;
+    if (shared && (rc = ensure(c, r.first, size_t(chunk_rays) * 32)) != PT_OK) return rc;
+    if ((rc = ensure(c, r.colour, size_t(chunk_rays) * p->spp * 16)) != PT_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(r.ro.p, ro, size_t(n) * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.rd.p, rd, size_t(n) * 12, hipMemcpyHostToDevice, c->stream));
+    if (p->sample0) {
+        HIPCHK(c, hipMemcpyAsync(r.mean.p, mean, size_t(n) * 12, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(r.moment.p, moment, size_t(n) * 12, hipMemcpyHostToDevice, c->stream));
+    }
+    PtRadiance R = {};
+    R.ro = r.ro.as<float>();
+    R.rd = r.rd.as<float>();
+    R.first = r.first.as<float4>();
+    R.colour = r.colour.as<float4>();
+    R.mean = mean ? r.mean.as<float>() : nullptr;
+    R.moment = moment ? r.moment.as<float>() : nullptr;
+    R.spp = p->spp;
+    R.sample0 = p->sample0;
+    R.seed = p->seed;
+    R.mode = p->mode;
+    r.klog.used = r.flog.used = 0;
+    for (uint32_t done = 0; done < n; done += chunk_rays) {
+        R.ray0 = done;
+        R.rays = std::min(chunk_rays, n - done);
+        HIPCHK(c, r.klog.record(c->stream));
+        if (shared) {
+            HIPCHK(c, r.flog.record(c->stream));
+            pt_launch_radiance(PtRadianceStage::First, L, R, c->stream);
+            HIPCHK(c, r.flog.record(c->stream));
+        }
+        pt_launch_radiance(PtRadianceStage::Samples, L, R, c->stream);
+        pt_launch_radiance(PtRadianceStage::Fold, L, R, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, r.klog.record(c->stream));
+    }
+    if (mean) HIPCHK(c, hipMemcpyAsync(mean, r.mean.p, size_t(n) * 12, hipMemcpyDeviceToHost, c->stream));
+    if (moment) HIPCHK(c, hipMemcpyAsync(moment, r.moment.p, size_t(n) * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
 int pt_accum_device_ptr(pt_ctx *c, void **dev_ptr, size_t *bytes) {
     if (!c || !dev_ptr || !bytes) return PT_ERR_INVALID;
     *dev_ptr = c->img.accum.p;

@@ -57,6 +57,33 @@ class Mesh:
             raise ValueError("mesh shape ordinal outside the program's shape ops")
         return table[self.shapes + 1]
 
+    def bake_rays(self, mode: str = "irradiance", offset: float = 0.03):
+        """The rays ``PathTracer.bake_mesh`` traces, one per vertex, float32
+        [n][3] each, from p + n * offset in float32 steps (0.03: the path's own
+        bounce offset): "irradiance" -> (origins, n), the normals a hemisphere
+        query draws its directions about; "view" -> (origins, -n), the ray of
+        a viewer looking straight at the vertex.  Host arithmetic only."""
+        if mode not in ("irradiance", "view"):
+            raise ValueError(f'mode must be "irradiance" or "view", got {mode!r}')
+        origins = self.positions + self.normals * np.float32(offset)
+        return origins, (self.normals.copy() if mode == "irradiance" else -self.normals)
+
+    def lit_colors(self, radiance, program=None, data: Optional[np.ndarray] = None) -> np.ndarray:
+        """Display colours from a ``bake_mesh`` result, float32 [n][3] in 0..1,
+        ready for ``save_ply(colors=)``: the mean of a "view" bake, or albedo x
+        mean (``vertex_colors(program, data)``) of an "irradiance" bake -- the
+        light a diffuse surface sends on -- then clip(., 0, 1) ** (1 / 2.2).
+        A NaN stays one (``save_ply`` paints it black)."""
+        mean = np.asarray(radiance.mean, np.float32)
+        if mean.shape != self.positions.shape:
+            raise ValueError(f"radiance must hold one row per vertex {self.positions.shape}, got {mean.shape}")
+        if radiance.mode == "hemisphere":
+            if program is None:
+                raise ValueError("an irradiance bake needs the program for the vertices' albedo")
+            mean = self.vertex_colors(program, data) * mean
+        with np.errstate(all="ignore"):
+            return (np.clip(mean, np.float32(0.0), np.float32(1.0)) ** np.float32(1.0 / 2.2)).astype(np.float32)
+
     def save_obj(self, path: str) -> None:
         """Wavefront OBJ: ``v``, ``vn`` and ``f a//a b//b c//c`` records (1-based)."""
         with open(path, "w") as f:

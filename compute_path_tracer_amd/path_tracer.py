@@ -37,6 +37,30 @@ class RayHits(NamedTuple):
     point: np.ndarray
 
 
+class Radiance(NamedTuple):
+    """What ``trace_radiance`` / ``bake_mesh`` return: ``mean`` and ``moment``
+    float32 [..., 3], the running mean of the samples' colours and of their
+    squares per ray, shaped like the query's leading dimensions; ``samples``,
+    how many they hold; ``mode`` ("ray" or "hemisphere").  A ray with a
+    non-finite component has NaN rows."""
+
+    mean: np.ndarray
+    moment: np.ndarray
+    samples: int
+    mode: str
+
+    @property
+    def variance(self) -> np.ndarray:
+        """The variance of the mean per ray, float32 [...]: the sum over r, g,
+        b of max(moment - mean * mean, 0) / (samples - 1) -- pt_read_variance's
+        formula in float32 on the host (the max drops a NaN; one sample has
+        no estimate: NaN or inf)."""
+        F = np.float32
+        with np.errstate(all="ignore"):
+            v = np.fmax(self.moment - self.mean * self.mean, F(0.0)) / F(self.samples - 1)
+            return (v[..., 0] + v[..., 1]) + v[..., 2]
+
+
 class Pick(NamedTuple):
     """One pixel's ``pick``: ``hit``, ``t``, ``point`` and ``normal`` (float32
     [3]), ``shape`` (ordinal, -1 = none) and ``node``, the editor's ``Shape``
@@ -579,6 +603,65 @@ class PathTracer:
         shape, hit = int(r.shape[0]), bool(r.hit[0])
         node = editor.shape_nodes()[shape] if editor is not None and hit and shape >= 0 else None
         return Pick(hit, float(r.t[0]), r.point[0], r.normal[0], shape, node)
+
+    # -- radiance queries (new: the light along a ray) ---------------------------
+    RADIANCE_MODES = {"ray": N.PT_RADIANCE_RAY, "hemisphere": N.PT_RADIANCE_HEMISPHERE}
+
+    def trace_radiance(self, origins, directions, spp: int, bounces: Optional[int] = None, seed: int = 0,
+                       mode: str = "ray", previous: Optional[Radiance] = None) -> Radiance:
+        """pt_trace_radiance: ``spp`` path-traced samples along each caller ray
+        (float [..., 3] each, the same shape), with the sky in force, folded
+        per ray into a running mean and second moment as the image folds
+        frames.  ``mode`` "ray": the path starts along the ray as given (a
+        direction is not normalised); "hemisphere": ``directions`` are surface
+        normals and each sample's first direction is drawn about its normal
+        (cosine-distributed for a unit normal: the mean is irradiance / pi).
+        ``bounces`` None: the settings' value.  ``seed`` picks the stream of
+        random numbers.  ``previous``: a ``Radiance`` of the same rays, seed
+        and mode to go on from -- 3 samples then 5 more equal 8 at once, bit
+        for bit.  A ray with a non-finite component is not traced (NaN)."""
+        o = np.ascontiguousarray(origins, np.float32)
+        d = np.ascontiguousarray(directions, np.float32)
+        if o.shape != d.shape or o.ndim < 1 or o.shape[-1] != 3:
+            raise ValueError(f"origins and directions must both be (..., 3), got {o.shape} and {d.shape}")
+        if mode not in self.RADIANCE_MODES:
+            raise ValueError(f"mode must be one of {sorted(self.RADIANCE_MODES)}, got {mode!r}")
+        lead, o, d = o.shape[:-1], o.reshape(-1, 3), d.reshape(-1, 3)
+        n, sample0 = len(o), 0
+        if previous is None:
+            mean, moment = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        else:
+            if previous.mean.shape != (*lead, 3) or previous.moment.shape != (*lead, 3) or previous.mode != mode:
+                raise ValueError("previous must be a Radiance of the same rays and mode")
+            sample0 = int(previous.samples)
+            mean = np.array(previous.mean, np.float32).reshape(n, 3)  # (copies: the call updates them in place)
+            moment = np.array(previous.moment, np.float32).reshape(n, 3)
+        p = N.RadianceParams(spp=int(spp), sample0=sample0, seed=int(seed) & 0xFFFFFFFF,
+                             bounces=int(self.settings.bounces if bounces is None else bounces),
+                             mode=self.RADIANCE_MODES[mode])
+        self._chk("pt_trace_radiance", self._L.pt_trace_radiance(self._ctx, N.fptr(o), N.fptr(d), n, ctypes.byref(p),
+                                                                  N.fptr(mean), N.fptr(moment)))
+        return Radiance(mean.reshape(*lead, 3), moment.reshape(*lead, 3), sample0 + int(spp), mode)
+
+    def irradiance(self, points, normals, spp: int, bounces: Optional[int] = None, seed: int = 0,
+                   offset: float = 0.03) -> np.ndarray:
+        """Irradiance at surface points, float32 [..., 3]: pi x the hemisphere
+        mean of ``trace_radiance`` from ``points + normals * offset`` about
+        ``normals`` (unit; float [..., 3] each).  0.03 is the path's own bounce
+        offset, so the probe starts where a path leaving the point would."""
+        F = np.float32
+        pts, nrm = np.asarray(points, F), np.asarray(normals, F)
+        r = self.trace_radiance(pts + nrm * F(offset), nrm, spp, bounces, seed, "hemisphere")
+        return r.mean * F(np.pi)
+
+    def bake_mesh(self, mesh: Mesh, spp: int, mode: str = "irradiance", offset: float = 0.03, **kw) -> Radiance:
+        """The light at every vertex of ``mesh``: ``trace_radiance`` over
+        ``mesh.bake_rays(mode, offset)`` -- "irradiance": the hemisphere about
+        the vertex normal; "view": what a viewer looking straight at the vertex
+        sees, emission and speculars included.  ``Mesh.lit_colors`` turns the
+        result into vertex colours.  ``kw``: ``bounces``, ``seed``, ``previous``."""
+        o, d = mesh.bake_rays(mode, offset)
+        return self.trace_radiance(o, d, spp, mode="hemisphere" if mode == "irradiance" else "ray", **kw)
 
     # -- point probes (tests: the scene's map() and bounds() per input) ---------
     PROBE_KINDS = {"interp": N.PT_PROBE_INTERP, "table": N.PT_PROBE_TABLE, "baked": N.PT_PROBE_BAKED}

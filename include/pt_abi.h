@@ -493,6 +493,58 @@ int pt_mesh_read(pt_ctx *ctx, float *positions, float *normals, int32_t *shapes,
 int pt_trace_rays(pt_ctx *ctx, const float *ro, const float *rd, uint32_t n, float *t, int32_t *shape, float *normal);
 int pt_pick_pixels(pt_ctx *ctx, const pt_constants *c, const pt_settings *s, const int32_t *xy, uint32_t n, float *t,
                    int32_t *shape, float *normal);
+/* Radiance queries (new): the light the path tracer computes
+ * along caller rays -- a light meter, an irradiance probe, a vertex to bake.
+ * n rays, ro and rd 3 floats each; p->spp samples per ray; mean and moment 3
+ * floats per ray, either may be NULL.  Per ray i and sample index
+ * k = p->sample0 + s, s in [0, spp):
+ *   rng = ((i * 1973 + seed * 9277 + k * 26699) mod 2^32) | 1: gen_rng's form
+ *     with the ray index, the caller's seed and the sample index for a, b and
+ *     frame; no jitter draw, no lens draw;
+ *   PT_RADIANCE_RAY: colour = path_trace(ro, rd, rng, bounces), debug 0, with
+ *     the sky in force (pt_set_sky: unlike the ray queries, this is a render);
+ *     rd is used as given, not normalised, as pt_trace_rays uses it;
+ *   PT_RADIANCE_HEMISPHERE: rd is a surface normal.  Two draws first, in the
+ *     order and f32 steps of the path's diffuse direction: uz = f01 * 2 - 1,
+ *     ua = f01 * 2pi, ur = sqrt(1 - uz * uz), (sa, ca) = sincos(ua),
+ *     d = normalize(rd + (ur * ca, ur * sa, uz)), then
+ *     colour = path_trace(ro, d, rng, bounces).  With a unit rd the directions
+ *     are cosine-distributed about it, so the mean estimates irradiance / pi;
+ *     a zero rd gives the uniform sphere;
+ *   the colours enter the ray's running values in the order of k with the
+ *     image's mix, last_clear = k: w = 1 / float(k + 1), mean = mean * (1 - w)
+ *     + colour * w, moment = moment * (1 - w) + colour * colour * w per channel
+ *     -- the bits an accumulation texel and its moment texel hold after the
+ *     same colours.  sample0 = 0: mean and moment are outputs only;
+ *     sample0 > 0: they are read as the running values first (in / out), so a
+ *     call of 8 samples equals one of 3 then one of 5 with sample0 = 3;
+ *   a non-finite colour enters the mix as it does in the image; a ray with a
+ *     non-finite component among its six is not marched: its mean and moment
+ *     are NaN in all channels, for any sample0.
+ * Nothing else is read or written: the image, the moments, the guides and
+ * their valid flag, the history, the mesh, the camera and pt_set_tiles neither
+ * enter nor change.  Blocking, on the context's stream.  Device memory does not
+ * grow with n * spp: the rays are walked in chunks of whole rays, at most
+ * "radiance_samples" samples in flight; the results are the same bits for every
+ * value of it.  n = 0 is a no-op.  Refused, in this order, before anything is
+ * read or written: PT_ERR_INVALID for a NULL context or p; for
+ * n > PT_RAYS_MAX; for NULL ro or rd (n > 0); for spp outside
+ * [1, PT_RADIANCE_MAX_SPP], sample0 + spp > 1 << 24, bounces < 0 or an unknown
+ * mode; for sample0 > 0 with a NULL mean or moment (a continuation needs
+ * both); PT_ERR_STATE without program or data.  The ahead-of-time interpreter
+ * serves it for every scene (no scene-specialised variant). */
+#define PT_RADIANCE_RAY 0        /* the sample's first segment is (ro, rd) as given */
+#define PT_RADIANCE_HEMISPHERE 1 /* rd is a surface normal: each sample's first direction is drawn about it */
+#define PT_RADIANCE_MAX_SPP 65536
+typedef struct pt_radiance_params { /* 20 bytes */
+    uint32_t spp;     /* 1..PT_RADIANCE_MAX_SPP samples added by this call */
+    uint32_t sample0; /* samples the in/out arrays already hold; 0 = start; sample0 + spp <= 1 << 24 */
+    uint32_t seed;    /* caller's stream */
+    int32_t bounces;  /* >= 0, as pt_settings.bounces */
+    int32_t mode;     /* PT_RADIANCE_* */
+} pt_radiance_params;
+int pt_trace_radiance(pt_ctx *ctx, const float *ro, const float *rd, uint32_t n, const pt_radiance_params *p, float *mean,
+                      float *moment);
 /* Tuning knobs: "kernel" (0 auto = 3, 1 simple one-path-per-lane, 2 tile-
  * resident wavefront state machine, 3 mask-binned passes: per bounce, the
  * rays of a chunk of frames are grouped by their bounds() check set before
@@ -519,7 +571,9 @@ int pt_pick_pixels(pt_ctx *ctx, const pt_constants *c, const pt_settings *s, con
  * stages a block's tile and halo in LDS for the iterations of step 1 and 2;
  * 0 loads every tap directly) and "mesh_skip" (pt_mesh_extract: 1, the
  * default, skips a brick whose centre value proves it holds no surface; 0
- * evaluates every brick).  Results are bit-identical for every value.
+ * evaluates every brick) and "radiance_samples" (pt_trace_radiance: samples
+ * in flight per chunk of whole rays, 65536..2^28, default 2^22; device memory
+ * = 16 B per sample).  Results are bit-identical for every value.
  * "moments" (0, the default: a dispatch launches what it always did; 1: the
  * second-moment image above is kept -- the image itself does not change). */
 int pt_set_option(pt_ctx *ctx, const char *key, int value);
@@ -539,7 +593,11 @@ int pt_set_option(pt_ctx *ctx, const char *key, int value);
  * last pt_sample_field's kernel), "mesh_ms" (the last pt_mesh_extract's
  * kernels, the sum of "mesh_skip_ms", "mesh_classify_ms", "mesh_scan_ms" and
  * "mesh_emit_ms"), "rays_ms" / "pick_ms" (the last pt_trace_rays' /
- * pt_pick_pixels' kernel), "guides_valid", "moments", "moments_valid", "moment_frames"
+ * pt_pick_pixels' kernel), "radiance_samples", "radiance_ms" (device time of
+ * the last pt_trace_radiance's kernels, summed over its chunks),
+ * "radiance_first_ms" (the shared first segments' part of it; 0 in hemisphere
+ * mode), "radiance_bytes" (device memory the radiance queries hold),
+ * "guides_valid", "moments", "moments_valid", "moment_frames"
  * (n; 0 while not valid), "variance_ms" (the last variance kernel, of
  * pt_read_variance or pt_denoise_guided), "guided_ms" (all iterations of the
  * last pt_denoise_guided, as "denoise_ms"), "history_valid", "history_views"
