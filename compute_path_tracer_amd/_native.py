@@ -109,6 +109,19 @@ class RadianceParams(Structure):
     _fields_ = [("spp", c_uint32), ("sample0", c_uint32), ("seed", c_uint32), ("bounces", c_int32), ("mode", c_int32)]
 
 
+PT_PREVIEW_MAX_SHADOW_STEPS = 64
+
+
+class PreviewParams(Structure):
+    """pt_preview_params: the key light, ambient gradient, shadow march, occlusion taps and highlight of
+    ``pt_render_preview`` (new)."""
+
+    _fields_ = [("light_dir", c_float * 3), ("light_color", c_float * 3), ("ambient_bottom", c_float * 3),
+                ("ambient_top", c_float * 3), ("shadow_steps", c_uint32), ("shadow_k", c_float),
+                ("shadow_cull", c_uint32), ("ao_strength", c_float), ("ao_radius", c_float), ("highlight", c_int32),
+                ("highlight_color", c_float * 3), ("highlight_mix", c_float)]
+
+
 class MeshDesc(Structure):
     """pt_mesh_desc: the grid, iso value and projection steps of ``pt_mesh_extract`` (new)."""
 
@@ -162,6 +175,7 @@ assert ctypes.sizeof(Constants) == 16 and ctypes.sizeof(Settings) == 20
 assert ctypes.sizeof(Camera) == 56 and ctypes.sizeof(Sky) == 52 and ctypes.sizeof(DenoiseParams) == 20
 assert ctypes.sizeof(GuidedParams) == 20 and ctypes.sizeof(TemporalParams) == 16
 assert ctypes.sizeof(MeshDesc) == 36 and ctypes.sizeof(MeshInfo) == 48 and ctypes.sizeof(RadianceParams) == 20
+assert ctypes.sizeof(PreviewParams) == 88
 assert ctypes.sizeof(SceneNode) == 132 and ctypes.sizeof(Op) == 132 and ctypes.sizeof(Aabb) == 56
 
 
@@ -234,6 +248,8 @@ SIGNATURES = {
     "pt_pick_pixels": (c_int, [_ctx, POINTER(Constants), POINTER(Settings), POINTER(c_int32), c_uint32, _f32p,
                                POINTER(c_int32), _f32p]),
     "pt_trace_radiance": (c_int, [_ctx, _f32p, _f32p, c_uint32, POINTER(RadianceParams), _f32p, _f32p]),
+    "pt_render_preview": (c_int, [_ctx, POINTER(Constants), POINTER(Settings), POINTER(PreviewParams), c_int, c_void_p,
+                                  c_size_t]),
     "pt_probe_map": (c_int, [_ctx, c_int, c_int, c_uint32, _f32p, _u64p, _f32p, _u64p, c_int, _f32p, POINTER(c_int32),
                              _u64p, _u64p]),
     "pt_probe_taps": (c_int, [_ctx, c_int, c_uint32, _f32p, _u64p, _f32p, _f32p, POINTER(c_int32), _u64p, _u64p]),

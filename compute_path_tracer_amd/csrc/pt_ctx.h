@@ -258,6 +258,12 @@ struct pt_ctx {
         EventLog klog, flog;
         size_t bytes() const { return ro.cap + rd.cap + mean.cap + moment.cap + first.cap + colour.cap; }
     } rad;
+    // preview shading (pt_render_preview): its own image, 16 B per pixel, grown on first use, and
+    // the timing of its kernel
+    struct Preview {
+        DevBuf img;
+        TimedSection time;
+    } preview;
     // the probes (pt_probe_map / pt_probe_taps / pt_probe_bounds, pt_map_probe.hip): the probe
     // modules loaded so far by their generated source, how many were compiled and in how many seconds, and the
     // staging of a call's inputs and outputs, grown on first use

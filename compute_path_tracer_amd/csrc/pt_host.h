@@ -57,6 +57,13 @@ struct PtRadiance {
 };
 enum class PtRadianceStage { First, Samples, Fold };
 void pt_launch_radiance(PtRadianceStage stage, const PtLaunch &L, const PtRadiance &R, hipStream_t stream);
+// preview shading (pt_render_preview): L as pt_launch_guides takes it but with the sky kept; the
+// caller's parameters as the host checked them, and the device image the texels go to, [height][width]
+struct PtPreview {
+    pt_preview_params p;
+    float4 *out;
+};
+void pt_launch_preview(const PtLaunch &L, const PtPreview &V, hipStream_t stream);
 
 // Expand (program, data[]) into the device tables (see pt_device.h).
 int pt_derive(const std::vector<pt_op> &ops, const std::vector<pt_aabb> &aabbs, const float *data, uint32_t n,

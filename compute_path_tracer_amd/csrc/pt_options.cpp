@@ -180,6 +180,8 @@ const Option kOptions[] = {
     OPT_GET("radiance_ms", log_ms(c, c->rad.klog, v)),
     OPT_GET("radiance_first_ms", log_ms(c, c->rad.flog, v)),
     OPT_READ("radiance_bytes", c->rad.bytes()),
+    // the last pt_render_preview's kernel, without its display pass (the call waited for it)
+    OPT_GET("preview_ms", section_ms(c, c->preview.time, false, v)),
     OPT_READ("guides_valid", c->dn.guides_valid ? 1.0 : 0.0),
     // second moments: whether the moment image and the accumulation image are one render's, and of how many frames;
     // the last variance kernel, and all iterations of the last pt_denoise_guided (without its variance and display passes)

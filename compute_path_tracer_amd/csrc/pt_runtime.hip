@@ -19,6 +19,7 @@
 #include "pt_ctx.h"
 #include "pt_device.h"
 #include "pt_math.h"
+#include "pt_post.h"
 
 static_assert(sizeof(pt_constants) == 16, "Constants is 16 B (path_tracer.rs:149-155)");
 static_assert(sizeof(pt_settings) == 20, "Settings is 20 B (path_tracer.rs:157-163)");
@@ -604,6 +605,58 @@ int pt_trace_radiance(pt_ctx *c, const float *ro, const float *rd, uint32_t n, c
     if (moment) HIPCHK(c, hipMemcpyAsync(moment, r.moment.p, size_t(n) * 12, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
+}
+
+// ---- preview shading ------------------------------------------------
+static_assert(sizeof(pt_preview_params) == 22 * 4, "pt_preview_params layout");
+
+// The launch block is a guide render's (every tile, a lens as its pinhole) but with the sky kept: a miss shows it.
+// The preview reads fov of the settings and nothing else, so the debug view and the bounce count do not enter.
+int pt_render_preview(pt_ctx *c, const pt_constants *k, const pt_settings *s, const pt_preview_params *p, int format,
+                      void *out, size_t bytes) {
+    if (!c) return PT_ERR_INVALID;
+    if (!k || !s) return fail(c, PT_ERR_INVALID, "null constants/settings");
+    if (!p) return fail(c, PT_ERR_INVALID, "null preview parameters");
+    if (format != PT_DISPLAY_RGBA32F && format != PT_DISPLAY_SRGB8 && format != PT_DENOISE_LINEAR)
+        return fail(c, PT_ERR_INVALID, "bad preview format");
+    for (const float *v3 : {p->light_dir, p->light_color, p->ambient_bottom, p->ambient_top, p->highlight_color})
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(v3[a])) return fail(c, PT_ERR_INVALID, "preview light, ambient and highlight colours must be finite");
+    if (p->shadow_steps > PT_PREVIEW_MAX_SHADOW_STEPS) return fail(c, PT_ERR_INVALID, "preview shadow_steps must be in [0, 64]");
+    if (!std::isfinite(p->shadow_k) || !(p->shadow_k > 0.0f)) return fail(c, PT_ERR_INVALID, "preview shadow_k must be finite and > 0");
+    if (p->shadow_cull > 1) return fail(c, PT_ERR_INVALID, "preview shadow_cull must be 0 or 1");
+    for (float v : {p->ao_strength, p->ao_radius})
+        if (!std::isfinite(v) || v < 0.0f) return fail(c, PT_ERR_INVALID, "preview ao_strength and ao_radius must be finite and >= 0");
+    if (p->highlight < -1) return fail(c, PT_ERR_INVALID, "preview highlight must be a shape ordinal or -1");
+    if (!(p->highlight_mix >= 0.0f && p->highlight_mix <= 1.0f)) return fail(c, PT_ERR_INVALID, "preview highlight_mix must lie in [0, 1]");
+    pt_settings view = *s;
+    view.debug = 0;    // (make_launch keeps the sky for the path-traced view only)
+    view.bounces = 0;  // (and refuses a negative count, which nothing here reads)
+    PtLaunch L;
+    int rc = make_query_launch(c, k, &view, L);
+    if (rc != PT_OK) return rc;
+    L.sky_mode = c->view.sky_mode;
+    const size_t texels = size_t(c->img.width) * c->img.height;
+    const size_t need = texels * (format == PT_DISPLAY_SRGB8 ? 4 : 16);
+    if (!out || bytes < need) return fail(c, PT_ERR_SIZE, "preview output buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    pt_ctx::Preview &pv = c->preview;
+    if ((rc = ensure(c, pv.img, std::max<size_t>(texels * 16, 16))) != PT_OK) return rc;
+    if (format != PT_DENOISE_LINEAR && (rc = ensure(c, c->img.display, std::max<size_t>(need, 16))) != PT_OK) return rc;
+    PtPreview V;
+    V.p = *p;
+    V.out = pv.img.as<float4>();
+    HIPCHK(c, pv.time.begin(c->stream));
+    pt_launch_preview(L, V, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, pv.time.end(c->stream));
+    const void *result = pv.img.p;
+    if (format != PT_DENOISE_LINEAR) {
+        pt_launch_display(pv.img.as<float>(), c->img.width, c->img.height, format, c->img.display.p, c->stream);
+        HIPCHK(c, hipGetLastError());
+        result = c->img.display.p;
+    }
+    return read_back(c, out, bytes, result, need, nullptr);
 }
 
 int pt_accum_device_ptr(pt_ctx *c, void **dev_ptr, size_t *bytes) {

@@ -18,7 +18,7 @@ import numpy as np
 from . import _native as N
 from .mesh import Mesh, mesh_grid
 from .sdf_editor import Program
-from .view import look_at_camera, sky_light
+from .view import look_at_camera, preview_light, sky_light
 
 
 class RayHits(NamedTuple):
@@ -603,6 +603,55 @@ class PathTracer:
         shape, hit = int(r.shape[0]), bool(r.hit[0])
         node = editor.shape_nodes()[shape] if editor is not None and hit and shape >= 0 else None
         return Pick(hit, float(r.t[0]), r.point[0], r.normal[0], shape, node)
+
+    # -- preview shading (new: a noise-free lit image for a viewport) ------------
+    def preview(self, light_direction=None, light_color=None, ambient=None, shadow_steps: int = 32,
+                shadow_softness: float = 8.0, shadow_cull: bool = False, ao_strength: float = 2.0,
+                ao_radius: float = 0.5, highlight=None, highlight_color=(1.0, 0.55, 0.1), highlight_mix: float = 0.5,
+                output: str = "linear", constants: Optional[N.Constants] = None) -> np.ndarray:
+        """pt_render_preview: the "solid" view of the scene under the camera
+        in force -- one jitter-free primary ray per pixel (``render_guides``'
+        rays), shaded with a key light and its sphere-traced soft shadow
+        (``shadow_steps`` map() calls at most, 0: none; ``shadow_softness``:
+        larger = harder edge), five occlusion taps out to ``ao_radius``
+        (``ao_strength`` 0: none) and an ambient gradient ``ambient`` =
+        (bottom, top) over the normal's height.  No random numbers and no
+        accumulation: the same bits on every call, at once after ``set_data``.
+        A miss shows the sky (black without one) with alpha 0; a hit has alpha 1.
+        ``light_direction`` points towards the light and is used as given;
+        arguments left None come from ``preview_light`` (the sky's sun, else a
+        light off the camera's shoulder).  ``shadow_cull`` marches the shadow
+        under the check[] set of its ray (cheaper; cuts penumbrae at box
+        silhouettes).  ``highlight``: a shape ordinal or a ``Pick`` whose
+        pixels are mixed ``highlight_mix`` of the way to ``highlight_color``.
+        ``output`` and the array returned are ``denoise``'s.  Nothing of the
+        context changes."""
+        if output not in self.DENOISE_OUTPUTS:
+            raise ValueError(f"output must be one of {sorted(self.DENOISE_OUTPUTS)}, got {output!r}")
+        default = None
+        if any(v is None for v in (light_direction, light_color, ambient)):
+            cam, dflt = self.get_camera()
+            sky, off = self.get_sky()
+            default = preview_light(None if dflt else cam, None if off else sky)
+        direction = default.direction if light_direction is None else light_direction
+        color = default.color if light_color is None else light_color
+        bottom, top = (default.ambient_bottom, default.ambient_top) if ambient is None else ambient
+        if isinstance(highlight, Pick):
+            highlight = highlight.shape if highlight.hit else None
+        p = N.PreviewParams(shadow_steps=int(shadow_steps), shadow_k=float(shadow_softness), shadow_cull=int(bool(shadow_cull)),
+                            ao_strength=float(ao_strength), ao_radius=float(ao_radius),
+                            highlight=-1 if highlight is None else int(highlight), highlight_mix=float(highlight_mix))
+        for name, v in (("light_dir", direction), ("light_color", color), ("ambient_bottom", bottom), ("ambient_top", top),
+                        ("highlight_color", highlight_color)):
+            if len(v) != 3:
+                raise ValueError(f"{name} must have three components, got {v!r}")
+            for k in range(3):
+                getattr(p, name)[k] = float(v[k])
+        c = self._constants(0) if constants is None else constants
+        out, po, nbytes = self._image(np.uint8 if output == "srgb8" else np.float32)
+        self._chk("pt_render_preview", self._L.pt_render_preview(self._ctx, ctypes.byref(c), ctypes.byref(self.settings),
+                                                                  ctypes.byref(p), self.DENOISE_OUTPUTS[output], po, nbytes))
+        return out
 
     # -- radiance queries (new: the light along a ray) ---------------------------
     RADIANCE_MODES = {"ray": N.PT_RADIANCE_RAY, "hemisphere": N.PT_RADIANCE_HEMISPHERE}

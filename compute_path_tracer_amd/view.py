@@ -1,8 +1,9 @@
-"""The view's host arithmetic: the ``pt_camera`` of a look-at pose and the
-``pt_sky`` of a gradient and a sun, in float32 steps.  No context, no library."""
+"""The view's host arithmetic: the ``pt_camera`` of a look-at pose, the
+``pt_sky`` of a gradient and a sun, and the preview's default key light, in
+float32 steps.  No context, no library."""
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -56,6 +57,45 @@ def look_at_camera(eye, target, up=(0.0, 1.0, 0.0), aperture: float = 0.0, focus
     for k in range(3):
         cam.origin[k], cam.right[k], cam.up[k], cam.forward[k] = e[k], right[k], cup[k], fwd[k]
     return cam
+
+
+class PreviewLight(NamedTuple):
+    """``preview_light``'s default key light: ``direction`` (towards the light,
+    unit), ``color``, and the ambient gradient's ``ambient_bottom`` (a normal
+    pointing straight down) and ``ambient_top`` (straight up), float32 [3] each."""
+
+    direction: np.ndarray
+    color: np.ndarray
+    ambient_bottom: np.ndarray
+    ambient_top: np.ndarray
+
+
+def preview_light(camera: Optional[N.Camera] = None, sky: Optional[N.Sky] = None) -> PreviewLight:
+    """The default light of ``PathTracer.preview`` under ``camera`` (None: the
+    reference's fixed one) and ``sky`` (None: none set), in float32 steps.
+    With a sky whose sun shines (a sun_color above 0) the direction is its
+    normalised sun_dir; otherwise a headlight off the camera's shoulder,
+    normalize(-forward + 0.5 up + 0.3 right).  The colour is (0.9, 0.9, 0.9).
+    The ambient gradient is the sky's bottom / top scaled by 0.35, or
+    (0.10, 0.10, 0.12) / (0.30, 0.32, 0.36) without a sky.  Host arithmetic
+    only (no context)."""
+    if sky is not None and any(float(v) > 0.0 for v in sky.sun_color):
+        d = np.array(list(sky.sun_dir), F)
+    else:
+        if camera is None:
+            r, u, f = np.array([1, 0, 0], F), np.array([0, 1, 0], F), np.array([0, 0, 1], F)
+        else:
+            r, u, f = (np.array(list(a), F) for a in (camera.right, camera.up, camera.forward))
+        d = (-f + F(0.5) * u) + F(0.3) * r
+    dl = _length(d)
+    if not (dl > 0 and np.isfinite(dl)):
+        raise ValueError("the light direction is zero or not finite")
+    d = (d / dl).astype(F)
+    if sky is not None:
+        bottom, top = np.array(list(sky.bottom), F) * F(0.35), np.array(list(sky.top), F) * F(0.35)
+    else:
+        bottom, top = np.array([0.10, 0.10, 0.12], F), np.array([0.30, 0.32, 0.36], F)
+    return PreviewLight(d, np.array([0.9, 0.9, 0.9], F), bottom.astype(F), top.astype(F))
 
 
 def sky_light(bottom, top=None, sun_direction=None, sun_color=(0.0, 0.0, 0.0), sun_angle: float = 0.0) -> N.Sky:

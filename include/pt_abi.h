@@ -545,6 +545,74 @@ typedef struct pt_radiance_params { /* 20 bytes */
 } pt_radiance_params;
 int pt_trace_radiance(pt_ctx *ctx, const float *ro, const float *rd, uint32_t n, const pt_radiance_params *p, float *mean,
                       float *moment);
+/* Preview shading (new): a noise-free lit image for a viewport
+ * -- one primary ray per pixel, a key light with a sphere-traced soft shadow,
+ * five distance taps of ambient occlusion, a hemisphere ambient term.  No
+ * random numbers, no accumulation, no history.  One RGBA32F texel per pixel of
+ * the context's size, every pixel whatever pt_set_tiles says, under the camera
+ * in force with a lens taken as its pinhole, aspect from c and fov from s: the
+ * rays of pt_render_guides.  Every step is one f32 operation in the order
+ * written, nothing contracted; gmin / gmax are fminf / fmaxf (a NaN operand is
+ * dropped); map(p, ck).d is the interpreted map() under the check[] set ck,
+ * "all" every entry set (as pt_sample_field); l = light_dir as given, not
+ * normalised.  For pixel (x, y):
+ *   (ro, rd) = the pixel's jitter-free primary ray; (t, n, mat) = its first hit
+ *     (bounds, CastRay, calc_normal normalised: n and t are g0's bits);
+ *   miss (t > FP): rgb = sky_radiance(rd) with a sky set (pt_set_sky), else 0;
+ *     alpha 0;
+ *   hit (a NaN t is a hit): hp = ro + rd * t; q = hp + n * 0.03;
+ *     ndl = gmax((n.x * l.x + n.y * l.y) + n.z * l.z, 0);
+ *     shadow: sh = 1; only if shadow_steps > 0 and ndl > 0: ck = bounds(q, l)
+ *       with shadow_cull, else all; s = 0.05; at most shadow_steps times:
+ *       d = map(q + l * s, ck).d; if d < 0.001: sh = 0, stop;
+ *       sh = gmin(sh, (shadow_k * d) / s); s = s + gmax(d, 0.02);
+ *       if s > 100: stop;
+ *     occlusion: ao = 1; only if ao_strength > 0: occ = 0, w = 1; for i = 0..4:
+ *       h = 0.01 + ao_radius * (float(i) * 0.25); d = map(hp + n * h, all).d;
+ *       occ = occ + (h - d) * w; w = w * 0.95;
+ *       then ao = gmin(gmax(1 - ao_strength * occ, 0), 1);
+ *     light: u = n.y * 0.5 + 0.5; per channel k:
+ *       amb = ambient_bottom + (ambient_top - ambient_bottom) * u;
+ *       lit = ndl * sh;
+ *       c = (col * ((amb * ao) + (light_color * lit))) + emis, col and emis
+ *       the hit material's albedo and emission (normalize(light) * brightness);
+ *     highlight: if highlight >= 0 and the hit shape's PT_OP_SHAPE ordinal (as
+ *       pt_pick_pixels reports it) equals it:
+ *       c = c + (highlight_color - c) * highlight_mix;
+ *     alpha 1.
+ * A NaN distance leaves sh as it is and steps on by 0.02; a NaN occ gives
+ * ao = 0; the only non-finite outputs are those the material or the sky
+ * carries.  The shadow march runs at all checks by default: its penumbra term
+ * needs the shapes near the ray, and bounds() knows only those whose box the
+ * ray's line enters, so shadow_cull = 1, the cheaper variant, cuts penumbrae
+ * at box silhouettes.  The occlusion taps are always at all checks.
+ * Formats, output sizes and row orders are pt_denoise's: PT_DENOISE_LINEAR, or
+ * PT_DISPLAY_RGBA32F / PT_DISPLAY_SRGB8 (the preview through the display
+ * pass).  Blocking, on the context's stream; out is caller-owned.  It writes
+ * its own 16 B per pixel device buffer (and the display pass's output buffer),
+ * held in the context from the first call on, and nothing else: the image, the
+ * moments, the guides and their valid flag, the history, the mesh, the camera
+ * and the sky neither change nor enter, except that the sky is read.  Refused,
+ * in this order, before anything is read or written: PT_ERR_INVALID for a NULL
+ * context, c, s or p, a bad format, or a field outside the ranges below (any
+ * non-finite float is); PT_ERR_STATE without program or data; PT_ERR_SIZE for
+ * a NULL or short out, as pt_display.  The ahead-of-time interpreter serves it
+ * for every scene (no scene-specialised variant). */
+#define PT_PREVIEW_MAX_SHADOW_STEPS 64
+typedef struct pt_preview_params { /* 88 bytes, 22 words */
+    float light_dir[3], light_color[3];
+    float ambient_bottom[3], ambient_top[3];
+    uint32_t shadow_steps; /* 0..PT_PREVIEW_MAX_SHADOW_STEPS; 0 = no shadow */
+    float shadow_k;        /* finite, > 0: larger = harder edge */
+    uint32_t shadow_cull;  /* 0 | 1 */
+    float ao_strength;     /* finite, >= 0; 0 = no taps */
+    float ao_radius;       /* finite, >= 0 */
+    int32_t highlight;     /* PT_OP_SHAPE ordinal as pt_pick_pixels reports it; -1 = none */
+    float highlight_color[3];
+    float highlight_mix;   /* in [0, 1] */
+} pt_preview_params;
+int pt_render_preview(pt_ctx *ctx, const pt_constants *c, const pt_settings *s, const pt_preview_params *p,
+                      int format, void *out, size_t bytes);
 /* Tuning knobs: "kernel" (0 auto = 3, 1 simple one-path-per-lane, 2 tile-
  * resident wavefront state machine, 3 mask-binned passes: per bounce, the
  * rays of a chunk of frames are grouped by their bounds() check set before
@@ -597,6 +665,8 @@ int pt_set_option(pt_ctx *ctx, const char *key, int value);
  * the last pt_trace_radiance's kernels, summed over its chunks),
  * "radiance_first_ms" (the shared first segments' part of it; 0 in hemisphere
  * mode), "radiance_bytes" (device memory the radiance queries hold),
+ * "preview_ms" (device time of the last pt_render_preview's kernel, without
+ * its display pass),
  * "guides_valid", "moments", "moments_valid", "moment_frames"
  * (n; 0 while not valid), "variance_ms" (the last variance kernel, of
  * pt_read_variance or pt_denoise_guided), "guided_ms" (all iterations of the
